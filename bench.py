@@ -11,8 +11,18 @@ computed there only (engine.py); --prune 0 runs every layer on every row.  `valu
 consumed by all ranks / wall time of the K timed steps (max over ranks),
 inputs resident in HBM.
 
+A plain run does only what that figure needs: set-up, W warm-up steps, the K
+timed steps, the output dump if asked for, the result line.  Everything else
+below (per-launch HIP events and the roofline, the parity leg, the quality
+leg, the CPU baseline) runs with --full only.
+
+--dump-outputs DIR writes what the last timed step left, as DIR/<name>.npy
+(dump_outputs): its loss and triples, and a fixed seeded sample of rows of
+the updated table and of the Adam moments.  The same arguments give the same
+inputs, so two builds can be compared array by array.
+
 Launch:
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
 With N > 1 and no WORLD_SIZE in the environment the script starts the N
 ranks itself (torch.distributed.run as a child process; this parent never
 touches the GPU) and exits with the ranks' status — the reference's
@@ -23,7 +33,7 @@ explicit form works too:
 --rehearse runs every rank on cuda:0 with gloo collectives (the N-rank code
 path on a one-GPU box; not a throughput measurement).
 
-Quality leg (--quality-steps S, default 3000): a second C2-sized graph with
+Quality leg (--full; --quality-steps S, default 3000): a second C2-sized graph with
 community structure (kind='cluster'), S training steps of the same engine
 from random init — with N > 1 through dist.DataParallel, every rank drawing B
 triples from its user shard — then rank 0 computes Recall@20 / NDCG@20 with
@@ -31,7 +41,7 @@ trainer.py / metric.py semantics (the rank-0 evaluation of ddp_lgcn.py:
 678-743) — reported beside the throughput, which is measured on the
 structureless uniform graph where any recall is chance.
 
-Parity leg (--parity 1): at N = 1 one more GPU step against the CPU oracle
+Parity leg (--full; --parity 1): at N = 1 one more GPU step against the CPU oracle
 from the same state; at N > 1 one more data-parallel step whose replicas must
 be bitwise equal (digests all-gathered) and whose table must match, at 1e-4,
 ONE single-process step of the union batch replayed on rank 0 from a snapshot
@@ -109,6 +119,14 @@ def parse(argv=None):
                          "1e-4)")
     ap.add_argument("--rehearse", action="store_true",
                     help="all ranks on cuda:0, gloo collectives (N-rank path on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: HIP events on the "
+                         "propagation launches (roofline, per-launch kinds), the parity leg, "
+                         "the quality leg and the CPU baseline (--parity, --quality-steps, "
+                         "--cpu-baseline, --event-every apply here only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left as DIR/<name>.npy "
+                         "(rank 0)")
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     if args.steps < 1:
@@ -468,6 +486,84 @@ def c2_workload(args) -> bool:
     return (args.users, args.items, args.edges) == (1_000_000, 100_000, 20_000_000)
 
 
+def launch_report(events, sampled: int, f1_rows: int, args) -> dict:
+    """The result line's per-launch entries from the timed steps' HIP events
+    ((start, end, kind, bytes) per propagation launch of the sampled steps)."""
+    per_kind = {}
+    for s, e, kind, nbytes in events:
+        ms = s.elapsed_time(e)
+        if kind[3]:
+            nbytes += 2 * f1_rows * args.dim * 4
+        key = kind[:3]  # one rocprof kernel per (mode, in_mask, row_mask)
+        d = per_kind.setdefault(key, [0, 0.0, 0])
+        d[0] += 1
+        d[1] += ms
+        d[2] += nbytes
+    t_prop = sum(v[1] for v in per_kind.values()) / sampled
+    dom = per_kind.get((0, False, False), [1, 1.0, 0])
+    avg_ms = dom[1] / dom[0]
+    avg_bytes = dom[2] / dom[0]
+    achieved = avg_bytes / (avg_ms * 1e-3) / 1e9
+    traffic, traffic_src = pmc_traffic(args)
+    unroll = {32: 2, 64: 4, 128: 4, 256: 8}.get(args.dim, 1)
+    return {
+        "roofline": {"bound": "hbm",
+                     "kernel": DOMINANT.replace("D, UNROLL", f"{args.dim}, {unroll}"),
+                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                     "traffic_source": traffic_src,
+                     "avg_launch_ms": round(avg_ms, 4),
+                     "algorithmic_bytes_per_launch": int(avg_bytes),
+                     "launches_per_step": round(dom[0] / sampled, 2),
+                     "timed_steps_sampled": sampled},
+        "roofline_hbm_counter": hbm_counter(traffic, avg_ms),
+        "propagation_ms_per_step": round(t_prop, 3),
+        "per_launch_kind": {
+            f"{KIND_NAMES[k[0]]}{'+inmask' if k[1] else ''}{'+rowmask' if k[2] else ''}":
+            {"launches_per_step": round(v[0] / sampled, 2), "avg_ms": round(v[1] / v[0], 4)}
+            for k, v in sorted(per_kind.items())},
+    }
+
+
+# ---------------------------------------------------------------- output dump
+
+DUMP_ROWS = 65536  # table rows kept per array: 3 x 65536 x D x 4 B = 48 MiB at D = 64
+DUMP_MAX_BYTES = 48 << 20  # cap of the three row samples together (larger D: fewer rows)
+
+
+def dump_rows(n_nodes: int, dim: int, seed: int) -> np.ndarray:
+    """The table rows a dump keeps: all of them when the three [rows, dim]
+    float32 samples fit DUMP_MAX_BYTES, else a sorted sample without
+    replacement that depends on (n_nodes, dim, seed) only."""
+    k = min(DUMP_ROWS, n_nodes, max(1, DUMP_MAX_BYTES // (3 * dim * 4)))
+    if k >= n_nodes:
+        return np.arange(n_nodes, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n_nodes, k, replace=False))
+
+
+def dump_outputs(path: str, loss, users, pos, neg, emb, adam, seed: int) -> dict:
+    """What a caller of the timed path holds after its last step, one .npy
+    per array: the step's loss (float64 [1]) and its triples (float64 [3, B]:
+    ids are exact), and the rows ``rows`` (float64 [k], dump_rows) of the
+    updated table and of Adam's two moments (float32 [k, D] each).  Returns
+    {name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    rows = dump_rows(int(emb.shape[0]), int(emb.shape[1]), seed)
+    idx = torch.from_numpy(rows).to(emb.device)
+    arrays = {
+        "loss": np.asarray([float(loss)], np.float64),
+        "triples": torch.stack([torch.as_tensor(x).reshape(-1) for x in (users, pos, neg)])
+        .cpu().numpy().astype(np.float64),
+        "rows": rows.astype(np.float64),
+        "table_rows": emb.detach()[idx].float().cpu().numpy(),
+        "exp_avg_rows": adam.exp_avg.detach()[idx].float().cpu().numpy(),
+        "exp_avg_sq_rows": adam.exp_avg_sq.detach()[idx].float().cpu().numpy(),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 # ---------------------------------------------------------------- quality leg
 
 def train_then_evaluate(step, steps: int, evaluate_fn, rank: int, world: int, sync=None,
@@ -601,9 +697,8 @@ def main(argv=None):
     def step(i):
         sample_triples(model.graph, B, args.seed, i * B, u, p, n, err, rank, world)
         if dp is None:
-            eng.train_step(emb, model.optim, u, p, n, cfg["decay"])
-        else:
-            dp.step(u, p, n, cfg["decay"])
+            return eng.train_step(emb, model.optim, u, p, n, cfg["decay"])
+        return dp.step(u, p, n, cfg["decay"])
 
     for i in range(args.warmup):
         step(i)
@@ -620,34 +715,42 @@ def main(argv=None):
         progress(f"dp calibration: {calib}")
     t_base = args.warmup if calib is None else nxt[0]
     dp_mode = dp.mode if dp is not None else "none"
-    ag_ms = dp.time_table_allgather() if (dp is not None and calib is None
+    ag_ms = dp.time_table_allgather() if (args.full and dp is not None and calib is None
                                           and dp.mode == "sharded") else None
     torch.cuda.synchronize()
-    # the live launch timing: HIP events on the launch stream around every
-    # propagation launch (and collective) of every k-th timed step — an event
-    # record idles the GPU for ~5 us (round-6 trace: ~50 us per C2 step with
-    # events on all 12 records), so the other steps run without them
+    # the live launch timing (--full): HIP events on the launch stream around
+    # every propagation launch (and collective) of every k-th timed step — an
+    # event record idles the GPU for ~5 us (round-6 trace: ~50 us per C2 step
+    # with events on all 12 records), so the other steps run without them
     every = max(1, args.event_every)
     prop_ev, comm_ev = [], []
     sampled = 0
+    loss = None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for j, i in enumerate(range(t_base, t_base + args.steps)):
-        on = j % every == every - 1 or (args.steps < every and j == args.steps - 1)
+        on = args.full and (j % every == every - 1
+                            or (args.steps < every and j == args.steps - 1))
         sampled += int(on)
         eng.prop_events = prop_ev if on else None
         if dp is not None:
             dp.comm_events = comm_ev if on else None
-        step(i)
+        loss = step(i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
     events, eng.prop_events = prop_ev, None
+    dumped = None
+    if args.dump_outputs:
+        if dp is not None:
+            dp.gather_optimizer_state()  # (sharded moments: current on own rows only)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, loss, u, p, n, emb, model.optim, args.seed)
     comm = None
-    if dp is not None:
+    if dp is not None and args.full:
         from furusato_recommend_amd.dist import _elapsed_ms
         comm_ms = dp._max_over_ranks(_elapsed_ms(comm_ev) / sampled)
         dp.comm_events = None
@@ -685,30 +788,19 @@ def main(argv=None):
     # A launch with an out_mask (forward layer 1 under pruning: layer sum
     # kept on F1 only) moves 2·|F1|·D·4 more bytes than launch_bytes counts;
     # |F1| is taken from the last step's mask (it varies by <0.5 % per step).
-    f1_rows = int((eng.bm_hop.view(torch.uint8)[: model.graph.n_nodes] != 0).sum())
-    per_kind = {}
-    for s, e, kind, nbytes in events:
-        ms = s.elapsed_time(e)
-        if kind[3]:
-            nbytes += 2 * f1_rows * args.dim * 4
-        key = kind[:3]  # one rocprof kernel per (mode, in_mask, row_mask)
-        d = per_kind.setdefault(key, [0, 0.0, 0])
-        d[0] += 1
-        d[1] += ms
-        d[2] += nbytes
-    t_prop = sum(v[1] for v in per_kind.values()) / sampled
-    dom = per_kind.get((0, False, False), [1, 1.0, 0])
-    avg_ms = dom[1] / dom[0]
-    avg_bytes = dom[2] / dom[0]
-    achieved = avg_bytes / (avg_ms * 1e-3) / 1e9
-    traffic, traffic_src = pmc_traffic(args)
+    launches = None
+    if args.full:
+        f1_rows = int((eng.bm_hop.view(torch.uint8)[: model.graph.n_nodes] != 0).sum())
+        launches = launch_report(events, sampled, f1_rows, args)
+        launches["frontier_F1_rows"] = f1_rows
 
     snap = None
     dp_parity = None
-    if rank == 0 and world == 1 and args.parity:
+    want_parity = args.full and args.parity
+    if rank == 0 and world == 1 and want_parity:
         progress("parity: GPU step from a host snapshot of the table and Adam state")
         snap = parity_snapshot(model, eng, emb, args, t_base + args.steps, rank, world)
-    elif world > 1 and args.parity:
+    elif world > 1 and want_parity:
         if rank == 0:
             progress("parity: one data-parallel step vs the union batch replayed on rank 0")
         i = t_base + args.steps
@@ -719,7 +811,7 @@ def main(argv=None):
         if rank == 0:
             progress(f"parity: {dp_parity}")
 
-    qsteps = max(0, args.quality_steps)
+    qsteps = max(0, args.quality_steps) if args.full else 0
     recall = None
     if qsteps > 0:
         del model, eng, emb, dp
@@ -727,7 +819,7 @@ def main(argv=None):
         recall = quality_leg(args, dev, qsteps, rank, world, dp_mode)
 
     cpu = parity = None
-    if rank == 0 and world == 1 and args.cpu_baseline != "off":
+    if rank == 0 and world == 1 and args.full and args.cpu_baseline != "off":
         cpu, parity = cpu_baseline(ds, args, u.cpu().numpy(), p.cpu().numpy(),
                                    n.cpu().numpy(), snap)
     elif snap is not None:
@@ -768,29 +860,16 @@ def main(argv=None):
                        "graph": args.kind, "dim": args.dim, "layers": args.layers,
                        "bpr_batch_per_rank": B, "global_batch": B * world,
                        "ranks": world, "parallelism": par},
-            "roofline": {"bound": "hbm",
-                         "kernel": DOMINANT.replace("D, UNROLL", f"{args.dim}, "
-                                                    f"{ {32: 2, 64: 4, 128: 4, 256: 8}.get(args.dim, 1)}"),
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "avg_launch_ms": round(avg_ms, 4),
-                         "algorithmic_bytes_per_launch": int(avg_bytes),
-                         "launches_per_step": round(dom[0] / sampled, 2),
-                         "timed_steps_sampled": sampled},
-            "roofline_hbm_counter": hbm_counter(traffic, avg_ms),
-            "propagation_ms_per_step": round(t_prop, 3),
-            "per_launch_kind": {
-                f"{KIND_NAMES[k[0]]}{'+inmask' if k[1] else ''}{'+rowmask' if k[2] else ''}":
-                {"launches_per_step": round(v[0] / sampled, 2), "avg_ms": round(v[1] / v[0], 4)}
-                for k, v in sorted(per_kind.items())},
+            "full": bool(args.full),
+            **(launches or {}),
             "prune": bool(args.prune),
-            "frontier_F1_rows": f1_rows,
             "recall": recall,
             "parity": parity,
             "cpu_baseline": cpu,
             "setup_s": round(t_setup, 2),
         }
+        if dumped is not None:
+            line["dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
         if comm is not None:
             line["comm"] = comm
         if args.rehearse:

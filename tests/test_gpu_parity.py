@@ -404,7 +404,10 @@ def test_zipf_long_rows_match_unsplit(d):
     gb = Graph.from_interactions(ds.trainUser, ds.trainItem, ds.n_users, ds.m_items, "cuda:0",
                                  split=1 << 30)
     assert ga.n_long > 0 and gb.n_long == 0
-    x = torch.randn(ga.n_nodes, d, device="cuda")
+    # a fixed input: the default CUDA generator seeds itself anew in every
+    # process, and the figure below moves with the draw
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    x = torch.randn(ga.n_nodes, d, device="cuda", generator=gen)
     outs = []
     for g in (ga, gb):
         e = PropagationEngine(g, d, 3, 64)

@@ -724,6 +724,43 @@ def test_bench_launcher_command():
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_plain_by_default_and_output_dump(tmp_path):
+    """A run without --full asks for none of the extra legs; --dump-outputs
+    writes float arrays that depend on the state and the seed only: the same
+    row sample on every call, within the 64 MB a dump may take."""
+    import types
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and a.dump_outputs is None and a.steps == 3
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path / "o")])
+    assert a.full and a.dump_outputs == str(tmp_path / "o")
+    # C2's table: the sample is fixed by (rows, dim, seed) and stays in bounds
+    r = bench.dump_rows(1_100_000, 64, 2020)
+    assert (r == bench.dump_rows(1_100_000, 64, 2020)).all()
+    assert len(np.unique(r)) == len(r) == 65536 and r.min() >= 0 and r.max() < 1_100_000
+    assert (np.diff(r) > 0).all() and (r != bench.dump_rows(1_100_000, 64, 2021)).any()
+    assert 3 * len(bench.dump_rows(11_000_000, 256, 0)) * 256 * 4 <= 48 << 20
+    assert (bench.dump_rows(10, 64, 0) == np.arange(10)).all()
+    g = torch.Generator().manual_seed(0)
+    emb = torch.randn(300, 8, generator=g)
+    adam = types.SimpleNamespace(exp_avg=torch.randn(300, 8, generator=g),
+                                 exp_avg_sq=torch.rand(300, 8, generator=g))
+    u, p, n = (torch.arange(k, k + 5, dtype=torch.int32) for k in (0, 10, 20))
+    shapes = bench.dump_outputs(str(tmp_path / "o"), torch.tensor([0.25]), u, p, n, emb, adam, 1)
+    got = {f[:-4]: np.load(tmp_path / "o" / f) for f in sorted(os.listdir(tmp_path / "o"))}
+    assert set(got) == set(shapes) == {"loss", "triples", "rows", "table_rows", "exp_avg_rows",
+                                       "exp_avg_sq_rows"}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) < 64 << 20
+    assert got["loss"].tolist() == [0.25]
+    assert (got["triples"] == np.stack([np.arange(k, k + 5) for k in (0, 10, 20)])).all()
+    rows = got["rows"].astype(np.int64)
+    assert (rows == np.arange(300)).all()
+    assert (got["table_rows"] == emb.numpy()[rows]).all()
+    assert (got["exp_avg_rows"] == adam.exp_avg.numpy()[rows]).all()
+    assert (got["exp_avg_sq_rows"] == adam.exp_avg_sq.numpy()[rows]).all()
+
+
 def test_bench_self_launch_two_ranks_gloo():
     """The real process tree on CPU: the parent spawns 2 ranks, they meet
     over gloo (with the watchdog timeout), rank 0 prints one JSON line."""

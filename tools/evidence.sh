@@ -12,7 +12,7 @@
 #   tests      the whole GPU suite in one process               -> pytest.log
 #   mark=EXPR  the GPU tests selected by -k EXPR ('+' for spaces: mark=a+or+b), verbose -> pytest_k.log
 #   smoke      __graft_entry__.smoke()                           -> smoke.log
-#   c2         the headline bench line (bench.py defaults: roofline, CPU
+#   c2         the headline bench line (bench.py --full: roofline, CPU
 #              baseline, oracle parity leg, Recall@20)           -> bench_c2.log
 #   c2quick    the C2 line without the CPU baseline and Recall legs (oracle parity kept)
 #   prof       C2 rocprofv3 passes: kernel stats, FETCH_SIZE, WRITE_SIZE of
@@ -75,10 +75,10 @@ for leg in $LEGS; do
       run 300 $E/smoke.log python -c "import __graft_entry__ as g; g.smoke()"
       tail -3 $E/smoke.log ;;
     c2)
-      run 700 $E/bench_c2.log python bench.py
+      run 700 $E/bench_c2.log python bench.py --full
       lines $E/bench_c2.log 600 ;;
     c2quick)
-      run 400 $E/bench_c2_quick.log python bench.py --cpu-baseline off --quality-steps 0
+      run 400 $E/bench_c2_quick.log python bench.py --full --cpu-baseline off --quality-steps 0
       lines $E/bench_c2_quick.log 600 ;;
     prof)
       PROF_OUT=$E/prof bash tools/profile.sh || exit 1
@@ -100,7 +100,7 @@ for leg in $LEGS; do
       run 300 $E/c4prof.log rocprofv3 --kernel-trace --stats -d $E/c4 -o run --output-format csv -- python3 tools/bench_sasrec.py --steps 10 --warmup 3 --cpu-baseline 0
       find $E/c4 -name "*kernel_trace.csv" -delete ;;
     zipf)
-      run 300 $E/bench_c2_zipf.log python bench.py --kind zipf --steps 20 --warmup 3 --cpu-baseline off --quality-steps 0 --parity 0
+      run 300 $E/bench_c2_zipf.log python bench.py --full --kind zipf --steps 20 --warmup 3 --cpu-baseline off --quality-steps 0 --parity 0
       lines $E/bench_c2_zipf.log
       run 300 $E/zipf.log rocprofv3 --kernel-trace --stats -d $E/zipf -o run --output-format csv -- python3 bench.py --kind zipf --steps 10 --warmup 3 --cpu-baseline off --quality-steps 0 --parity 0
       find $E/zipf -name "*kernel_trace.csv" -delete ;;
@@ -112,10 +112,10 @@ for leg in $LEGS; do
       # union-batch replay on rank 0) and the DataParallel Recall@20 leg
       N=${leg#rehearse}
       Q=$([ "$N" = 8 ] && echo 1000 || echo 3000)
-      run 700 $E/bench_c2_rehearse_dp$N.log python bench.py --gpus $N --rehearse --steps 5 --warmup 2 --quality-steps $Q
+      run 700 $E/bench_c2_rehearse_dp$N.log python bench.py --full --gpus $N --rehearse --steps 5 --warmup 2 --quality-steps $Q
       lines $E/bench_c2_rehearse_dp$N.log 600 ;;
     c5)
-      run 900 $E/bench_c5.log python bench.py --users 10000000 --items 1000000 --edges 200000000 --dim 256 --steps 5 --warmup 2 --cpu-baseline off --quality-steps 0 --parity 0
+      run 900 $E/bench_c5.log python bench.py --full --users 10000000 --items 1000000 --edges 200000000 --dim 256 --steps 5 --warmup 2 --cpu-baseline off --quality-steps 0 --parity 0
       lines $E/bench_c5.log ;;
     pmc_tg)
       timeout -k 10 200 python -u tools/tg_sum_bytes.py > $E/tg_counts.json 2> $E/tg_counts.log || { echo "tg counts rc=$?"; exit 1; }
