@@ -65,6 +65,16 @@ class Prop(Structure):
     ]
 
 
+class Sweep(Structure):
+    """mirec_sweep_t (column-sweep layout of the item rows)."""
+    _fields_ = [
+        ("row0", c_int64), ("n_rows", c_int64), ("n_src", c_int64),
+        ("tile_rows", c_int32), ("group_rows", c_int32), ("groups", c_int32),
+        ("n_tiles", c_int32), ("band_rows", c_int32), ("_pad", c_int32),
+        ("gptr", c_void_p), ("ent", c_void_p),
+    ]
+
+
 class RowGradGroup(Structure):
     """mirec_row_grad_group_t (one group of table-gradient row contributions)."""
     _fields_ = [
@@ -99,6 +109,13 @@ SIGNATURES = {
                                     POINTER(c_int64), c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
     "mirec_propagate": (c_int, [POINTER(CSR), POINTER(Prop), c_void_p]),
+    "mirec_propagate_sweep": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(Sweep), c_void_p]),
+    "mirec_sweep_sizeof": (c_size_t, []),
+    "mirec_sweep_shape": (c_int, [c_int64, c_int32, c_int32, POINTER(c_int32),
+                                  POINTER(c_int32)]),
+    "mirec_sweep_build": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32,
+                                  c_int32, c_void_p, c_void_p]),
+    "mirec_sweep_groups": (c_int, [c_int32]),
     "mirec_prescale": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "mirec_shard_pack": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_int64,
                                  c_void_p, c_void_p]),
@@ -350,6 +367,8 @@ def _load():
         raise ImportError(f"struct layout mismatch: lib {[x.value for x in sizes]} vs {want}")
     if lib.mirec_row_grad_group_size() != ctypes.sizeof(RowGradGroup):
         raise ImportError("struct layout mismatch: mirec_row_grad_group_t")
+    if lib.mirec_sweep_sizeof() != ctypes.sizeof(Sweep):
+        raise ImportError("struct layout mismatch: mirec_sweep_t")
     return lib
 
 

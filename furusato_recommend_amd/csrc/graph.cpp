@@ -162,6 +162,88 @@ extern "C" int mirec_csr_sort_rows(const int64_t *rowptr, const int32_t *col, in
   return MIREC_OK;
 }
 
+extern "C" size_t mirec_sweep_sizeof(void) { return sizeof(mirec_sweep_t); }
+
+extern "C" int mirec_sweep_shape(int64_t n_rows, int32_t tile_rows, int32_t group_rows,
+                                 int32_t *n_tiles, int32_t *groups) {
+  if (n_rows < 0 || tile_rows <= 0 || group_rows <= 0 || n_tiles == nullptr || groups == nullptr)
+    return MIREC_ERR_ARG;
+  const int64_t nt = (n_rows + tile_rows - 1) / tile_rows;
+  if (nt >= INT32_MAX) return MIREC_ERR_RANGE;
+  *n_tiles = (int32_t)nt;
+  *groups = (tile_rows + group_rows - 1) / group_rows;
+  return MIREC_OK;
+}
+
+// Column-sweep layout (mirec_sweep_t).  Stream (tile, group) covers
+// consecutive rows, so its entries occupy the same index range as in the CSR
+// (gptr comes straight from rowptr) and the layout is a permutation inside
+// each range: sorted by (column, CSR position), i.e. a stable sort by column.
+// Tiles are split over up to 16 threads.
+extern "C" int mirec_sweep_build(const int64_t *rowptr, const int32_t *col, int64_t row0,
+                                 int64_t n_rows, int64_t n_src, int32_t tile_rows,
+                                 int32_t group_rows, int64_t *gptr, int32_t *ent) {
+  int32_t n_tiles = 0, groups = 0;
+  if (rowptr == nullptr || gptr == nullptr || row0 < 0 || n_src < 0) return MIREC_ERR_ARG;
+  const int rc = mirec_sweep_shape(n_rows, tile_rows, group_rows, &n_tiles, &groups);
+  if (rc != MIREC_OK) return rc;
+  const int64_t base = rowptr[row0], total = rowptr[row0 + n_rows] - base;
+  if (total < 0 || (total > 0 && (col == nullptr || ent == nullptr))) return MIREC_ERR_ARG;
+  auto stream_row = [&](int64_t t, int64_t g) {  // first row (block-relative) of a stream
+    const int64_t tile_end = std::min<int64_t>((t + 1) * tile_rows, n_rows);
+    return std::min<int64_t>(t * tile_rows + g * group_rows, tile_end);
+  };
+  for (int64_t t = 0; t < n_tiles; ++t)
+    for (int64_t g = 0; g < groups; ++g)
+      gptr[t * groups + g] = rowptr[row0 + stream_row(t, g)] - base;
+  gptr[(int64_t)n_tiles * groups] = total;
+  const int n_thr = (int)std::max<int64_t>(
+      1, std::min<int64_t>(16, std::min<int64_t>((int64_t)std::thread::hardware_concurrency(),
+                                                 total / (1 << 16) + 1)));
+  std::vector<int> bad(n_thr, 0);
+  auto work = [&](int th) {
+    std::vector<uint64_t> key;
+    std::vector<int32_t> lrow;
+    for (int64_t t = th; t < n_tiles; t += n_thr) {
+      for (int64_t g = 0; g < groups; ++g) {
+        const int64_t r0 = stream_row(t, g);
+        const int64_t r1 = g + 1 < groups ? stream_row(t, g + 1)
+                                          : std::min<int64_t>((t + 1) * tile_rows, n_rows);
+        const int64_t e0 = rowptr[row0 + r0], e1 = rowptr[row0 + r1];
+        if (e1 - e0 >= INT32_MAX) {
+          bad[th] = 1;
+          return;
+        }
+        key.resize(e1 - e0);
+        lrow.resize(e1 - e0);
+        for (int64_t r = r0; r < r1; ++r)
+          for (int64_t e = rowptr[row0 + r]; e < rowptr[row0 + r + 1]; ++e) {
+            const int32_t c = col[e];
+            if (c < 0 || c >= n_src) {
+              bad[th] = 1;
+              return;
+            }
+            key[e - e0] = ((uint64_t)(uint32_t)c << 32) | (uint64_t)(e - e0);
+            lrow[e - e0] = (int32_t)(r - t * tile_rows);
+          }
+        std::sort(key.begin(), key.end());
+        int32_t *o = ent + 2 * (e0 - base);
+        for (size_t k = 0; k < key.size(); ++k) {
+          o[2 * k] = (int32_t)(key[k] >> 32);
+          o[2 * k + 1] = lrow[(uint32_t)key[k]];
+        }
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < n_thr; ++t) th.emplace_back(work, t);
+  work(0);
+  for (auto &x : th) x.join();
+  for (int b : bad)
+    if (b) return MIREC_ERR_RANGE;
+  return MIREC_OK;
+}
+
 // Per-user positive CDF for the weighted samplers (the sample_pow option,
 // negative_sample.py:53-56): probs[e - rowptr[0]] = the probability of entry
 // e of its user row (rows 0 .. n_users - 1, the allPos order), each row's

@@ -463,6 +463,155 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void prop_finalize(PropK a, co
   row_epilogue<D>(a, row, t, sub);
 }
 
+// ---- column sweep (mirec_sweep_t): the item rows of a full PRESCALED launch.
+// A uniformly gathered 256 MB user block gets nothing from an XCD's 4 MB L2:
+// every neighbour row comes over the fabric.  Here a workgroup owns a tile of
+// consecutive rows, accumulators in LDS, and walks the tile's entries in
+// ascending SOURCE column; every workgroup sweeps the user block in the same
+// direction at about the same pace, so the rows being gathered at any moment
+// are a window of a few MB, which an XCD fetches once and then serves from
+// its L2.  Each LPR-lane group owns a run of the tile's rows and a stream of
+// their entries sorted by column (built on the host): no row is shared, no
+// atomics, no reduction, one fixed summation order per row (ascending column,
+// duplicate edges in CSR order).
+//
+// Pacing: the column range is cut into bands; a wave passes from band b to
+// b + 1 through a bare s_barrier (no counter wait: it orders when loads are
+// ISSUED, nothing is handed over through memory), so a workgroup's waves stay
+// within a band of each other while row loads stay in flight across the band
+// boundary.  Every wave executes exactly n_bands - 1 barriers whatever its
+// streams hold.  Workgroups never wait for each other: they stay together
+// only because they start together and carry equal work per band; nothing
+// depends on which of them are resident.
+constexpr int kSweepThreads = 512;
+constexpr int kSweepLdsMax = 64 * 1024;
+
+struct SweepK {
+  const int64_t *gptr;
+  const long long *ent;  // (lrow << 32) | col per entry
+  int64_t row0;
+  int64_t n_rows;
+  int32_t tile_rows;
+  int32_t group_rows;
+  int32_t groups;
+  int32_t band_rows;
+  int32_t n_bands;
+};
+
+template <int D, int U>
+__device__ __forceinline__ void sweep_work(const PropK &a, const SweepK &s) {
+  constexpr int LPR = D / 4;
+  static_assert(LPR % U == 0 && LPR <= 64, "a chunk of LPR entries is U-row batches");
+  extern __shared__ float4 sweep_acc[];  // [tile_rows][LPR]
+  const int lane = threadIdx.x & 63;
+  const int sub = threadIdx.x % LPR;
+  const int grp = threadIdx.x / LPR;  // lane group of the workgroup
+  const int gbase = (lane / LPR) * LPR;
+  const int64_t tile_row0 = (int64_t)blockIdx.x * s.tile_rows;
+  const int tile_len = (int)min((int64_t)s.tile_rows, s.n_rows - tile_row0);
+  const bool active = grp < s.groups;
+  const int lr0 = active ? min(grp * s.group_rows, tile_len) : 0;
+  const int lr1 = active ? min(lr0 + s.group_rows, tile_len) : 0;
+  for (int lr = lr0; lr < lr1; ++lr) sweep_acc[lr * LPR + sub] = f4_zero();
+  int64_t pos = 0, end = 0;
+  if (active) {
+    const int64_t sidx = (int64_t)blockIdx.x * s.groups + grp;
+    pos = s.gptr[sidx];
+    end = s.gptr[sidx + 1];
+  }
+  // entries past the stream's end read as column INT32_MAX (beyond every band)
+  constexpr long long kNone = 0x7fffffffll;
+  // Every global load below is unconditional (a clamped address, the value
+  // dropped by a select): with loads under branches the compiler cannot
+  // count them and waits for ALL outstanding loads at each use, which
+  // serialises the batches.
+  const int64_t last = max(end - 1, (int64_t)0);  // ent holds >= 1 entry
+  long long cur = __builtin_nontemporal_load(s.ent + min(pos + sub, last));
+  if (pos + sub >= end) cur = kNone;
+  int band = 0;  // wave-uniform
+  int64_t hi = s.band_rows;
+  float4 pv[U];
+  int pr[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    pv[u] = f4_zero();
+    pr[u] = -1;
+  }
+  // chunks of the wave's longest stream (wave-uniform trip count)
+  int n_chunks = (int)((end - pos + LPR - 1) / LPR);
+#pragma unroll
+  for (int m = LPR; m < 64; m <<= 1) n_chunks = max(n_chunks, __shfl_xor(n_chunks, m));
+  n_chunks = __builtin_amdgcn_readfirstlane(n_chunks);
+#pragma unroll 1
+  for (int c = 0; c < n_chunks; ++c) {
+    // the next chunk's entries, one chunk ahead
+    long long nxt = __builtin_nontemporal_load(s.ent + min(pos + LPR + sub, last));
+    if (pos + LPR + sub >= end) nxt = kNone;
+    const int ccol = (int)(cur & 0xffffffffll);
+    const int crow = (int)(cur >> 32);
+#pragma unroll
+    for (int k = 0; k < LPR; k += U) {
+      // the wave enters the next band once none of its groups has an entry
+      // of the current one left to issue
+      const int nc = __shfl(ccol, gbase + k);
+      while (band + 1 < s.n_bands && __ballot((int64_t)nc < hi) == 0ull) {
+        __builtin_amdgcn_s_barrier();
+        ++band;
+        hi += s.band_rows;
+      }
+      float4 v[U];
+      int r[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int j = __shfl(ccol, gbase + k + u);
+        const int rr = __shfl(crow, gbase + k + u);
+        const bool ok = pos + k + u < end;
+        r[u] = ok ? rr : -1;  // a slot past the end reads row 0 and is dropped
+        v[u] = ld4(a.x_in + (int64_t)(ok ? j : 0) * D + sub * 4);
+      }
+      // add the PREVIOUS batch (its loads were issued a batch ago) while
+      // this one is in flight; a row's terms are added in stream order
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (pr[u] >= 0) {
+          float4 *p = &sweep_acc[pr[u] * LPR + sub];
+          *p = f4_add(*p, pv[u]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        pv[u] = v[u];
+        pr[u] = r[u];
+      }
+    }
+    pos += LPR;
+    cur = nxt;
+  }
+  while (band + 1 < s.n_bands) {  // every wave executes the same number of barriers
+    __builtin_amdgcn_s_barrier();
+    ++band;
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (pr[u] >= 0) {
+      float4 *p = &sweep_acc[pr[u] * LPR + sub];
+      *p = f4_add(*p, pv[u]);
+    }
+  }
+  // rows are private to their group (same lanes wrote and read them)
+  for (int lr = lr0; lr < lr1; ++lr)
+    row_epilogue<D>(a, s.row0 + tile_row0 + lr, sweep_acc[lr * LPR + sub], sub);
+}
+
+// (the body is a separate always-inline function: the shuffle and ballot
+// wrappers inline into it, and it into the kernel, across the kernel's
+// packed-f32 target attribute)
+template <int D, int U>
+__global__ __launch_bounds__(kSweepThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+MIREC_NO_PK_F32 void prop_sweep_kernel(PropK a, SweepK s) {
+  sweep_work<D, U>(a, s);
+}
+
 template <int D, int UNROLL, int MODE, bool MASKED>
 static void launch_main(dim3 grid, hipStream_t st, const PropK &k) {
   if (k.row_mask != nullptr)
@@ -520,8 +669,66 @@ __global__ __launch_bounds__(256) void prescale_kernel(const float *__restrict__
 
 }  // namespace mirec
 
+namespace mirec {
+
+// The sweep path's qualifying rule; the graph-side part
+// (bipartite, enough rows, a source block larger than L2) is decided where
+// the layout is built.
+static bool sweep_qualifies(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sweep_t *sw) {
+  if (sw == nullptr || p->dim != 64) return false;
+  if (p->in_mode != MIREC_IN_PRESCALED) return false;
+  if (p->in_mask != nullptr || p->row_mask != nullptr || p->row_list != nullptr) return false;
+  if (c->n_seg > 0) return false;
+  if (sw->gptr == nullptr || sw->ent == nullptr || sw->n_rows <= 0 || sw->n_tiles <= 0)
+    return false;
+  if (sw->row0 < 0 || sw->row0 + sw->n_rows != c->n_rows || sw->n_src > c->n_rows) return false;
+  if (sw->tile_rows <= 0 || sw->group_rows <= 0 || sw->band_rows <= 0) return false;
+  if (sw->groups <= 0 || sw->groups > kSweepThreads / (64 / 4)) return false;
+  if ((int64_t)sw->groups * sw->group_rows < sw->tile_rows) return false;
+  if ((int64_t)sw->n_tiles * sw->tile_rows < sw->n_rows) return false;
+  if ((int64_t)sw->tile_rows * 64 * 4 > kSweepLdsMax) return false;
+  return true;
+}
+
+// Item rows by the sweep kernel, rows [0, row0) by the row kernel.
+template <int D, int UNROLL>
+static int launch_sweep(const mirec_csr_t *c, const PropK &k, const mirec_sweep_t *sw,
+                        hipStream_t st) {
+  SweepK s;
+  s.gptr = sw->gptr;
+  s.ent = reinterpret_cast<const long long *>(sw->ent);
+  s.row0 = sw->row0;
+  s.n_rows = sw->n_rows;
+  s.tile_rows = sw->tile_rows;
+  s.group_rows = sw->group_rows;
+  s.groups = sw->groups;
+  s.band_rows = sw->band_rows;
+  s.n_bands = (int32_t)std::max<int64_t>(1, (sw->n_src + sw->band_rows - 1) / sw->band_rows);
+  const size_t lds = (size_t)sw->tile_rows * D * sizeof(float);
+  hipLaunchKernelGGL((prop_sweep_kernel<D, 4>), dim3((unsigned)sw->n_tiles), dim3(kSweepThreads),
+                     lds, st, k, s);
+  MIREC_LAUNCH_CHECK();
+  if (sw->row0 == 0) return MIREC_OK;
+  mirec_csr_t head = *c;
+  head.n_rows = sw->row0;
+  PropK kh = k;
+  kh.n_rows = sw->row0;  // the last wave's groups past row0 - 1 stay idle
+  return launch_prop<D, UNROLL>(&head, kh, 0, MIREC_IN_PRESCALED, st);
+}
+
+}  // namespace mirec
+
+extern "C" int mirec_sweep_groups(int32_t dim) {
+  return dim == 64 ? mirec::kSweepThreads / (64 / 4) : 0;
+}
+
 extern "C" int mirec_propagate(const mirec_csr_t *c, const mirec_prop_t *p,
                                mirec_stream_t stream) {
+  return mirec_propagate_sweep(c, p, nullptr, stream);
+}
+
+extern "C" int mirec_propagate_sweep(const mirec_csr_t *c, const mirec_prop_t *p,
+                                     const mirec_sweep_t *sw, mirec_stream_t stream) {
   using namespace mirec;
   MIREC_CHECK_ARG(c != nullptr && p != nullptr);
   MIREC_CHECK_ARG(c->rowptr != nullptr && c->dinv != nullptr && c->n_rows >= 0);
@@ -577,6 +784,7 @@ extern "C" int mirec_propagate(const mirec_csr_t *c, const mirec_prop_t *p,
   k.wide_count = p->wide_count;
   const int64_t cap = p->row_list_cap;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (sweep_qualifies(c, p, sw)) return launch_sweep<64, 4>(c, k, sw, st);
   switch (p->dim) {
     case 4: return launch_prop<4, 1>(c, k, cap, p->in_mode, st);
     case 8: return launch_prop<8, 1>(c, k, cap, p->in_mode, st);

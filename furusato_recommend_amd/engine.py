@@ -278,6 +278,10 @@ class PropagationEngine:
         # tuning switches (tools/bench_variants.py)
         self.use_hop_list = True      # F1 launches walk hop_list (else: byte map)
         self.reuse_prescaled = True   # fused update writes the next x~_0
+        # full PRESCALED launches gather the item rows with the column sweep
+        # (graphs that qualify, Graph.sweep_layout; else the row kernel)
+        self.use_sweep = True
+        self.sweep = graph.sweep_layout(self.dim)
         # first backward layer's neighbour filter: "slot" (one dependent load;
         # best for one batch), "bytemap" (S byte map, then the slot of the
         # hits), "dense" (seed rows scattered into a zero [N, D] table and
@@ -362,8 +366,10 @@ class PropagationEngine:
         if ev is not None:
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record()
-        check(lib.mirec_propagate(g.csr_ptr(), ctypes.byref(p), _lib.stream_handle()),
-              "propagate")
+        sw = self.sweep if (self.use_sweep and g is self.g) else None
+        check(lib.mirec_propagate_sweep(g.csr_ptr(), ctypes.byref(p),
+                                        sw.ptr() if sw is not None else None,
+                                        _lib.stream_handle()), "propagate")
         if ev is not None:
             e.record()
             kind = (in_mode, in_mask is not None, row_mask is not None, out_mask is not None)
@@ -419,6 +425,12 @@ class PropagationEngine:
                                               self.list_counts.data_ptr(), _lib.stream_handle()),
                   "mask_compact_pair")
         self._masks_ready = True
+
+    def set_sweep_sizes(self, tile_rows: int | None = None, group_rows: int | None = None,
+                        band_rows: int | None = None):
+        """Rebuild the sweep layout with explicit sizes (tuning; tests force
+        many tiles and bands on a small graph).  All None = the defaults."""
+        self.sweep = self.g.sweep_layout(self.dim, tile_rows, group_rows, band_rows)
 
     def _wide_bits(self) -> torch.Tensor:
         """Bit v of word v // 32: node v's degree > narrow_max (the row lists'

@@ -16,11 +16,29 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CSR, check, lib
+from ._lib import CSR, Sweep, check, lib
 
 # Rows longer than this are split into segments (load balance on skewed
 # item popularity).  2048 neighbours x 256 B = 512 KiB of gather per segment.
 DEFAULT_SPLIT = 2048
+
+# Column sweep of the item rows (csrc/prop.hip): the source
+# columns are paced in bands of this many bytes of user rows, a workgroup's
+# LDS accumulators are capped at SWEEP_LDS_BYTES, and a user block that fits
+# one XCD's L2 (4 MiB) gains nothing from the sweep.
+SWEEP_BAND_BYTES = 1 << 20
+SWEEP_LDS_BYTES = 64 << 10
+SWEEP_L2_BYTES = 4 << 20
+
+
+class SweepLayout:
+    """Device arrays of a column-sweep layout and their descriptor."""
+    gptr: torch.Tensor
+    ent: torch.Tensor
+    desc: Sweep
+
+    def ptr(self):
+        return ctypes.byref(self.desc)
 
 
 class Graph:
@@ -135,6 +153,69 @@ class Graph:
                   "csr_from_coo(transpose)")
             g.transpose = cls(rowptr_t, col_t, dinv, n_nodes, 0, device, split)
         return g
+
+    # ------------------------------------------------------------ column sweep
+    def sweep_layout(self, dim: int, tile_rows: int | None = None,
+                     group_rows: int | None = None, band_rows: int | None = None):
+        """The column-ordered layout of the item rows (mirec_sweep_t) for
+        width ``dim``, or None when the graph does not qualify: not a
+        bipartite user–item graph, a long row anywhere (n_seg > 0), no sweep
+        kernel for the width; and, with the default sizes, fewer item rows
+        than CUs or a user block that fits one XCD's L2.  Defaults: two tiles
+        per CU (all resident at once), half as many lane groups as the kernel has,
+        bands of SWEEP_BAND_BYTES of user rows.  Explicit sizes (tests, tuning)
+        skip the two size conditions.  Built once per (graph, sizes)."""
+        key = ("sweep", dim, tile_rows, group_rows, band_rows)
+        cache = self.__dict__.setdefault("_sweeps", {})
+        if key in cache:
+            return cache[key]
+        cache[key] = lay = self._build_sweep(dim, tile_rows, group_rows, band_rows)
+        return lay
+
+    def _build_sweep(self, dim, tile_rows, group_rows, band_rows):
+        nu, mi = self.n_users, self.m_items
+        max_groups = int(lib.mirec_sweep_groups(dim))
+        if not (self.symmetric and nu > 0 and mi > 0 and nu + mi == self.n_nodes):
+            return None
+        if self.n_seg > 0 or max_groups == 0 or self.device.type != "cuda":
+            return None
+        explicit = not (tile_rows is None and group_rows is None and band_rows is None)
+        row_bytes = dim * 4
+        max_tile = SWEEP_LDS_BYTES // row_bytes
+        if not explicit:
+            n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
+            if mi < n_cu or nu * row_bytes <= SWEEP_L2_BYTES:
+                return None
+        if tile_rows is None:
+            n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
+            tile_rows = min(max_tile, max(1, -(-mi // (2 * n_cu))))
+        if group_rows is None:
+            # half the workgroup's lane groups, each with twice the rows: 1.315
+            # against 1.353 ms per full C2 launch (DESIGN.md §12.5)
+            group_rows = -(-tile_rows // max(1, max_groups // 2))
+        if band_rows is None:
+            band_rows = max(1, SWEEP_BAND_BYTES // row_bytes)
+        tile_rows, group_rows, band_rows = int(tile_rows), int(group_rows), int(band_rows)
+        n_tiles, groups = ctypes.c_int32(0), ctypes.c_int32(0)
+        check(lib.mirec_sweep_shape(mi, tile_rows, group_rows, ctypes.byref(n_tiles),
+                                    ctypes.byref(groups)), "sweep_shape")
+        if tile_rows > max_tile or groups.value > max_groups or band_rows <= 0:
+            raise ValueError(f"sweep sizes out of range: tile_rows {tile_rows} (max {max_tile}), "
+                             f"{groups.value} groups (max {max_groups}), band_rows {band_rows}")
+        n_ent = int(self.rowptr_host[nu + mi] - self.rowptr_host[nu])
+        gptr = np.empty(n_tiles.value * groups.value + 1, np.int64)
+        ent = np.zeros(2 * max(n_ent, 1), np.int32)
+        check(lib.mirec_sweep_build(self.rowptr_host.ctypes.data, self.col_host.ctypes.data, nu,
+                                    mi, nu, tile_rows, group_rows, gptr.ctypes.data,
+                                    ent.ctypes.data), "sweep_build")
+        lay = SweepLayout()
+        lay.gptr = torch.from_numpy(gptr).to(self.device)
+        lay.ent = torch.from_numpy(ent).to(self.device)
+        lay.desc = Sweep(row0=nu, n_rows=mi, n_src=nu, tile_rows=tile_rows,
+                         group_rows=group_rows, groups=groups.value, n_tiles=n_tiles.value,
+                         band_rows=band_rows, _pad=0, gptr=lay.gptr.data_ptr(),
+                         ent=lay.ent.data_ptr())
+        return lay
 
     def set_positive_probs(self, probs) -> None:
         """Per-user positive probabilities for the samplers (the sample_pow

@@ -210,6 +210,61 @@ typedef struct mirec_prop {
 int mirec_propagate(const mirec_csr_t *csr, const mirec_prop_t *p,
                     mirec_stream_t stream);
 
+/* Column-sweep layout of a block of CSR rows (the item rows of a bipartite
+ * graph), built once per graph on the host (csrc/graph.cpp) and read by the
+ * sweep kernel of csrc/sweep.hip.  The rows [row0, row0 + n_rows) are cut
+ * into n_tiles tiles of tile_rows consecutive rows (the last one shorter),
+ * one workgroup each; a tile's rows are cut into `groups` runs of group_rows
+ * consecutive rows, one lane group each.  Stream s = tile * groups + group
+ * holds the entries of its rows as (source column, row index inside the
+ * tile) pairs at ent[2 * e], ent[2 * e + 1], e in [gptr[s], gptr[s + 1]),
+ * sorted by column, stable: every row's entries appear in ascending column
+ * order with duplicate edges in CSR order, which is the order the kernel
+ * sums them in.  Every column lies in [0, n_src) (the source block, a
+ * bipartite graph's user rows); the kernel paces its walk over it in bands
+ * of band_rows columns.  All pointers are device pointers. */
+typedef struct mirec_sweep {
+  int64_t row0;
+  int64_t n_rows;
+  int64_t n_src;
+  int32_t tile_rows;
+  int32_t group_rows;
+  int32_t groups;
+  int32_t n_tiles;
+  int32_t band_rows;
+  int32_t _pad;
+  const int64_t *gptr; /* [n_tiles * groups + 1] */
+  const int32_t *ent;  /* [2 * (rowptr[row0 + n_rows] - rowptr[row0])] */
+} mirec_sweep_t;
+
+size_t mirec_sweep_sizeof(void);
+
+/* Host: n_tiles = ceil(n_rows / tile_rows) and groups = ceil(tile_rows /
+ * group_rows) of a layout with these parameters (array sizes for
+ * mirec_sweep_build). */
+int mirec_sweep_shape(int64_t n_rows, int32_t tile_rows, int32_t group_rows,
+                      int32_t *n_tiles, int32_t *groups);
+
+/* Host: fill gptr [n_tiles * groups + 1] and ent [2 * entries] (host arrays)
+ * from the host CSR.  MIREC_ERR_RANGE if an entry's column is outside
+ * [0, n_src) (the rows do not gather from the source block only). */
+int mirec_sweep_build(const int64_t *rowptr, const int32_t *col, int64_t row0,
+                      int64_t n_rows, int64_t n_src, int32_t tile_rows,
+                      int32_t group_rows, int64_t *gptr, int32_t *ent);
+
+/* Lane groups a sweep workgroup has at this width (the layout's `groups`
+ * may not exceed it), 0 if the sweep kernel is not built for the width. */
+int mirec_sweep_groups(int32_t dim);
+
+/* mirec_propagate with the rows of `sw` gathered by the sweep kernel and the
+ * rows [0, sw->row0) by the row kernel, on the same stream, when the launch
+ * qualifies: in_mode PRESCALED, no in_mask / row_mask / row list, no long-row
+ * segments (csr->n_seg == 0), sw->row0 + sw->n_rows == csr->n_rows and the
+ * width has a sweep kernel.  Anything else (sw == NULL included) is exactly
+ * mirec_propagate.  Per row the sum runs in ascending source column. */
+int mirec_propagate_sweep(const mirec_csr_t *csr, const mirec_prop_t *p,
+                          const mirec_sweep_t *sw, mirec_stream_t stream);
+
 /* out = dinv ⊙ x row-wise (the pre-scaled layer-0 input x~_0). */
 int mirec_prescale(const float *x, const float *dinv, int64_t n_rows,
                    int32_t dim, float *out, mirec_stream_t stream);

@@ -24,6 +24,7 @@ VARIANTS = {
     "no_hop_list": {"use_hop_list": False},
     "no_reuse": {"reuse_prescaled": False},
     "mask_only": {"use_hop_list": False, "reuse_prescaled": False},
+    "no_sweep": {"use_sweep": False},
 }
 
 
@@ -81,7 +82,7 @@ def main():
         print(json.dumps({"variant": name, "ms_per_step": round(dt * 1e3, 4),
                           "launch_ms": launches, "prop_sum_ms": round(sum(launches), 4)}))
         for k in VARIANTS[name]:
-            setattr(eng, k, {"use_hop_list": True, "reuse_prescaled": True}[k])
+            setattr(eng, k, True)
 
 
 if __name__ == "__main__":
