@@ -36,7 +36,7 @@ class CSR(Structure):
         ("_pad", c_int32), ("n_long", c_int64), ("n_seg", c_int64),
         ("long_rows", c_void_p), ("long_segptr", c_void_p),
         ("seg_row", c_void_p), ("seg_beg", c_void_p),
-        ("col_sorted", c_void_p), ("n_sorted", c_int64),
+        ("col_sorted", c_void_p), ("n_sorted", c_int64), ("val", c_void_p),
     ]
 
 
@@ -102,6 +102,7 @@ SIGNATURES = {
     "mirec_csr_sort_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "mirec_csr_from_coo": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                    c_void_p, c_void_p]),
+    "mirec_csr_entry_order": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
     "mirec_parse_interactions": (c_int, [c_void_p, c_int64, c_int64, c_int32, POINTER(c_int64),
                                          POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
                                          c_void_p, c_void_p, c_void_p]),
@@ -116,6 +117,7 @@ SIGNATURES = {
     "mirec_sweep_build": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32,
                                   c_int32, c_void_p, c_void_p]),
     "mirec_sweep_groups": (c_int, [c_int32]),
+    "mirec_edge_dot": (c_int, [POINTER(CSR), c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "mirec_prescale": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "mirec_shard_pack": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_int64,
                                  c_void_p, c_void_p]),

@@ -97,6 +97,21 @@ extern "C" int mirec_csr_from_coo(const int64_t *src, const int64_t *dst, int64_
   return MIREC_OK;
 }
 
+extern "C" int mirec_csr_entry_order(const int64_t *dst, int64_t nnz, int64_t n_nodes,
+                                     int64_t *perm) {
+  if (nnz < 0 || n_nodes <= 0) return MIREC_ERR_ARG;
+  if (nnz > 0 && (dst == nullptr || perm == nullptr)) return MIREC_ERR_ARG;
+  std::vector<int64_t> cur(n_nodes + 1, 0);
+  for (int64_t e = 0; e < nnz; ++e) {
+    if (dst[e] < 0 || dst[e] >= n_nodes) return MIREC_ERR_RANGE;
+    ++cur[dst[e] + 1];
+  }
+  for (int64_t v = 0; v < n_nodes; ++v) cur[v + 1] += cur[v];
+  // the same counting sort as mirec_csr_from_coo, writing the edge's index
+  for (int64_t e = 0; e < nnz; ++e) perm[cur[dst[e]]++] = e;
+  return MIREC_OK;
+}
+
 extern "C" int mirec_csr_long_rows(const int64_t *rowptr, int64_t n_rows, int32_t split,
                                    int64_t *n_long, int64_t *n_seg, int32_t *long_rows,
                                    int64_t *long_segptr, int32_t *seg_row, int64_t *seg_beg) {

@@ -30,6 +30,12 @@
 // a finalize launch, so a Zipf-skewed item cannot serialise the grid (the
 // row phase leaves them to their segments entirely).
 //
+// Edge weights (csr->val, optional): prop_kernel<.., MODE + kWeighted, ..> is
+// the same walk with every term multiplied by its entry's value (A_ij = sum
+// of val over the entries j -> i); the unweighted instantiations are the
+// earlier ones, instruction for instruction.
+// mirec_edge_dot gives the gradient with respect to the values.
+//
 // Epilogue (per row, LPR lanes): z = dinv_i * sum + seed[slot_i];
 // xs_out = dinv_i * z (next layer's pre-scaled input);
 // o = (z + addend)/divisor + seed2[slot_i]; out = o or Adam(param; grad=o).
@@ -69,7 +75,12 @@ struct PropK {
   int32_t narrow_max;        // rows up to this degree are gathered group-per-row
   const int32_t *wide_list;  // rows gathered by a whole workgroup each (list mode)
   const int32_t *wide_count;
+  const float *val;          // [nnz] per-entry weight (WEIGHTED instantiations only)
 };
+
+// prop_kernel's MODE argument with this bit set is the edge-weighted walk
+// (the unweighted instantiations keep their names: MODE 0..3).
+constexpr int kWeighted = 4;
 
 __device__ __forceinline__ bool bit_set(const uint8_t *bm, int64_t i) { return bm[i] != 0; }
 
@@ -85,7 +96,11 @@ __device__ __forceinline__ void adam_elem(float &p, float &m, float &v, float g,
 // Sum of the input rows listed in col[beg, end) (pre-scaled / raw x dinv_j /
 // sparse seeds x dinv_j), restricted to in_mask when MASKED.  Returns this
 // lane's group partial (a disjoint subset of the neighbours).
-template <int D, int UNROLL, int MODE, bool MASKED>
+// WEIGHTED: entry e's term is multiplied by val[e]; the value is loaded next
+// to its column and follows it through the compaction, and the per-neighbour
+// weight becomes val (PRESCALED, which then takes the fma form) or
+// val * dinv_j (RAW, SPARSE).  Same order of terms as the unweighted sum.
+template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED>
 __device__ __forceinline__ float4 gather_rows(const PropK &a, int64_t beg, int64_t end,
                                               int lane) {
   constexpr int LPR = D / 4;
@@ -98,6 +113,8 @@ __device__ __forceinline__ float4 gather_rows(const PropK &a, int64_t beg, int64
   for (int64_t base = beg; base < end; base += 64) {
     int cnt = (int)min((int64_t)64, end - base);
     int myc = lane < cnt ? a.col[base + lane] : 0;
+    float myv = 1.f;
+    if constexpr (WEIGHTED) myv = lane < cnt ? a.val[base + lane] : 0.f;
     // SPARSE: the seed-row slot itself is the filter (slot >= 0 <=> node in
     // S), one dependent load less than a byte-map test followed by the slot
     // (with an in_mask, SPARSE tests the byte map first and reads the slot
@@ -114,6 +131,8 @@ __device__ __forceinline__ float4 gather_rows(const PropK &a, int64_t beg, int64
         const int dst = ok ? below : nv + (lane - below);
         myc = __builtin_amdgcn_ds_permute(dst << 2, myc);
         if (slot_filter) myr = __builtin_amdgcn_ds_permute(dst << 2, myr);
+        if (WEIGHTED)
+          myv = __int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int(myv)));
       }
       cnt = nv;
     }
@@ -123,6 +142,7 @@ __device__ __forceinline__ float4 gather_rows(const PropK &a, int64_t beg, int64
     if (MODE == MIREC_IN_RAW || MODE == MIREC_IN_SPARSE) {
       if (lane < cnt) myw = a.dinv[myc];
     }
+    if (WEIGHTED) myw = lane < cnt ? myv * myw : 0.f;
     if (MODE == MIREC_IN_SPARSE && myr < 0) {  // byte map set without a seed row
       myr = 0;
       myw = 0.f;
@@ -134,7 +154,7 @@ __device__ __forceinline__ float4 gather_rows(const PropK &a, int64_t beg, int64
       for (int u = 0; u < UNROLL; ++u) {
         const int idx = k + u * G + grp;
         const int j = __shfl(myr, idx & 63);
-        w[u] = (MODE != MIREC_IN_PRESCALED) ? __shfl(myw, idx & 63) : 1.f;
+        w[u] = (MODE != MIREC_IN_PRESCALED || WEIGHTED) ? __shfl(myw, idx & 63) : 1.f;
         if (idx < cnt)
           v[u] = ld4(src + (int64_t)j * D + sub * 4);
         else
@@ -142,7 +162,7 @@ __device__ __forceinline__ float4 gather_rows(const PropK &a, int64_t beg, int64
       }
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
-        if (MODE != MIREC_IN_PRESCALED)
+        if (MODE != MIREC_IN_PRESCALED || WEIGHTED)
           acc = f4_fma(w[u], v[u], acc);
         else
           acc = f4_add(acc, v[u]);
@@ -158,7 +178,7 @@ __device__ __forceinline__ float4 gather_rows(const PropK &a, int64_t beg, int64
 // latency-bound short rows get G x the memory-level parallelism of the
 // wave-per-row path.  Control flow is group-uniform; shuffles stay inside
 // the group.
-template <int D, int UNROLL, int MODE, bool MASKED>
+template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED>
 __device__ __forceinline__ float4 gather_narrow(const PropK &a, int64_t beg, int64_t end,
                                                 int lane) {
   constexpr int LPR = D / 4;
@@ -171,6 +191,8 @@ __device__ __forceinline__ float4 gather_narrow(const PropK &a, int64_t beg, int
   for (int64_t c = beg; c < end; c += LPR) {
     int cnt = (int)min((int64_t)LPR, end - c);
     int myc = sub < cnt ? a.col[c + sub] : 0;
+    float myv = 1.f;
+    if constexpr (WEIGHTED) myv = sub < cnt ? a.val[c + sub] : 0.f;
     const bool slot_filter = MODE == MIREC_IN_SPARSE && a.in_mask == nullptr;
     int myr = slot_filter ? (sub < cnt ? a.slot[myc] : -1) : myc;
     if (MASKED) {
@@ -185,6 +207,8 @@ __device__ __forceinline__ float4 gather_narrow(const PropK &a, int64_t beg, int
         const int dst = gbase + (ok ? below : nv + (sub - below));
         myc = __builtin_amdgcn_ds_permute(dst << 2, myc);
         if (slot_filter) myr = __builtin_amdgcn_ds_permute(dst << 2, myr);
+        if (WEIGHTED)
+          myv = __int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int(myv)));
       }
       cnt = nv;
     }
@@ -194,6 +218,7 @@ __device__ __forceinline__ float4 gather_narrow(const PropK &a, int64_t beg, int
     if (MODE == MIREC_IN_RAW || MODE == MIREC_IN_SPARSE) {
       if (sub < cnt) myw = a.dinv[myc];
     }
+    if (WEIGHTED) myw = sub < cnt ? myv * myw : 0.f;
     if (MODE == MIREC_IN_SPARSE && myr < 0) {  // byte map set without a seed row
       myr = 0;
       myw = 0.f;
@@ -206,7 +231,7 @@ __device__ __forceinline__ float4 gather_narrow(const PropK &a, int64_t beg, int
         const int idx = k + u;
         const int srcl = gbase + (idx & (LPR - 1));
         const int j = __shfl(myr, srcl);
-        w[u] = (MODE != MIREC_IN_PRESCALED) ? __shfl(myw, srcl) : 1.f;
+        w[u] = (MODE != MIREC_IN_PRESCALED || WEIGHTED) ? __shfl(myw, srcl) : 1.f;
         if (idx < cnt)
           v[u] = ld4(src + (int64_t)j * D + sub * 4);
         else
@@ -214,7 +239,7 @@ __device__ __forceinline__ float4 gather_narrow(const PropK &a, int64_t beg, int
       }
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
-        if (MODE != MIREC_IN_PRESCALED)
+        if (MODE != MIREC_IN_PRESCALED || WEIGHTED)
           acc = f4_fma(w[u], v[u], acc);
         else
           acc = f4_add(acc, v[u]);
@@ -277,7 +302,7 @@ constexpr int kWavesPerBlock = 4;
 // short list does not pay for its host-side capacity in empty waves.
 // MASKED = in_mask filter on neighbours, ROWMASK = row_mask filter on rows
 // (separate instantiations so profiles tell full and pruned launches apart).
-template <int D, int UNROLL, int MODE, bool MASKED, bool ROWMASK>
+template <int D, int UNROLL, int MODE, bool MASKED, bool ROWMASK, bool WEIGHTED>
 __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nrows,
                                           int64_t row_waves) {
   constexpr int LPR = D / 4;
@@ -303,7 +328,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
     }
     const int64_t deg = have ? end - beg : 0;
     if (G > 1 && __ballot(deg > a.narrow_max) == 0ull) {
-      float4 s = gather_narrow<D, NARROW_UNROLL, MODE, MASKED>(a, beg, end, lane);
+      float4 s = gather_narrow<D, NARROW_UNROLL, MODE, MASKED, WEIGHTED>(a, beg, end, lane);
       if (have) row_epilogue<D>(a, row, s, sub);
       return;
     }
@@ -314,7 +339,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
       const int32_t r = __shfl(row, src);
       const int64_t rb = __shfl((long long)beg, src);
       const int64_t re = __shfl((long long)end, src);
-      float4 s = gather_rows<D, UNROLL, MODE, MASKED>(a, rb, re, lane);
+      float4 s = gather_rows<D, UNROLL, MODE, MASKED, WEIGHTED>(a, rb, re, lane);
       s = combine_groups<D>(s);
       if (lane < LPR) row_epilogue<D>(a, r, s, sub);
     }
@@ -325,7 +350,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
     if (ROWMASK && !bit_set(a.row_mask, row)) return;
     const int64_t beg = a.seg_beg[sg];
     const int64_t end = min(beg + (int64_t)a.split, a.rowptr[row + 1]);
-    float4 s = gather_rows<D, UNROLL, MODE, MASKED>(a, beg, end, lane);
+    float4 s = gather_rows<D, UNROLL, MODE, MASKED, WEIGHTED>(a, beg, end, lane);
     s = combine_groups<D>(s);
     if (lane < LPR) st4(a.partial + sg * D + sub * 4, s);
   }
@@ -335,7 +360,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
 // quarter of the row's entries, the four wave sums are added in wave order
 // through LDS (deterministic), wave 0 runs the epilogue.  Block-uniform
 // control flow (contains barriers).
-template <int D, int UNROLL, int MODE, bool MASKED>
+template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED>
 __device__ __forceinline__ void block_row(const PropK &a, int32_t row) {
   constexpr int LPR = D / 4;
   __shared__ float4 red[kWavesPerBlock - 1][LPR];
@@ -346,7 +371,7 @@ __device__ __forceinline__ void block_row(const PropK &a, int32_t row) {
   if (a.split > 0 && end - beg > a.split) return;  // segments handle it (uniform)
   const int64_t q = (end - beg + kWavesPerBlock - 1) / kWavesPerBlock;
   const int64_t wb = min(beg + wid * q, end), we = min(wb + q, end);
-  float4 s = gather_rows<D, UNROLL, MODE, MASKED>(a, wb, we, lane);
+  float4 s = gather_rows<D, UNROLL, MODE, MASKED, WEIGHTED>(a, wb, we, lane);
   s = combine_groups<D>(s);
   if (wid > 0 && lane < LPR) red[wid - 1][sub] = s;
   __syncthreads();
@@ -359,13 +384,13 @@ __device__ __forceinline__ void block_row(const PropK &a, int32_t row) {
 }
 
 // One row gathered by one wave.
-template <int D, int UNROLL, int MODE, bool MASKED>
+template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED>
 __device__ __forceinline__ void wave_row(const PropK &a, int32_t row) {
   constexpr int LPR = D / 4;
   const int lane = threadIdx.x & 63;
   const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
   if (a.split > 0 && end - beg > a.split) return;  // segments handle it
-  float4 s = gather_rows<D, UNROLL, MODE, MASKED>(a, beg, end, lane);
+  float4 s = gather_rows<D, UNROLL, MODE, MASKED, WEIGHTED>(a, beg, end, lane);
   s = combine_groups<D>(s);
   if (lane < LPR) row_epilogue<D>(a, row, s, lane % LPR);
 }
@@ -378,19 +403,22 @@ constexpr int64_t kListBlocks = 8192;
 
 // Occupancy floor (waves per SIMD): keeps the register allocator at <= 72
 // VGPRs so 7-8 waves per SIMD keep enough gathers in flight.
-template <int D, int UNROLL, int MODE, bool MASKED, bool ROWMASK>
+// MODE_W = in_mode, + kWeighted for an edge-weighted launch (csr->val).
+template <int D, int UNROLL, int MODE_W, bool MASKED, bool ROWMASK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8)))
 MIREC_NO_PK_F32 void prop_kernel(PropK a) {
+  constexpr int MODE = MODE_W & 3;
+  constexpr bool WEIGHTED = (MODE_W & kWeighted) != 0;
   constexpr int G = 64 / (D / 4);
   // wave index made provably uniform (SGPR): loop control stays scalar
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if constexpr (!ROWMASK) {
-    prop_work<D, UNROLL, MODE, MASKED, ROWMASK>(a, (int64_t)blockIdx.x * kWavesPerBlock + wid,
-                                                a.n_rows, a.row_waves);
+    prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED>(
+        a, (int64_t)blockIdx.x * kWavesPerBlock + wid, a.n_rows, a.row_waves);
   } else {
     if (a.row_list == nullptr) {
-      prop_work<D, UNROLL, MODE, MASKED, ROWMASK>(a, (int64_t)blockIdx.x * kWavesPerBlock + wid,
-                                                  a.n_rows, a.row_waves);
+      prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED>(
+          a, (int64_t)blockIdx.x * kWavesPerBlock + wid, a.n_rows, a.row_waves);
       return;
     }
     // List mode: the list lengths are known only on the device, so the grid
@@ -410,14 +438,15 @@ MIREC_NO_PK_F32 void prop_kernel(PropK a) {
     for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
       if (b < wide_blocks) {
         if constexpr (WPB == 1) {
-          block_row<D, UNROLL, MODE, MASKED>(a, a.wide_list[b]);
+          block_row<D, UNROLL, MODE, MASKED, WEIGHTED>(a, a.wide_list[b]);
         } else {
           const int64_t i = b * WPB + wid;
-          if (i < n_wide) wave_row<D, UNROLL, MODE, MASKED>(a, a.wide_list[i]);
+          if (i < n_wide) wave_row<D, UNROLL, MODE, MASKED, WEIGHTED>(a, a.wide_list[i]);
         }
       } else {
         const int64_t w = (b - wide_blocks) * kWavesPerBlock + wid;
-        if (w < waves) prop_work<D, UNROLL, MODE, MASKED, ROWMASK>(a, w, nrows, row_waves);
+        if (w < waves)
+          prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED>(a, w, nrows, row_waves);
       }
     }
   }
@@ -614,6 +643,16 @@ MIREC_NO_PK_F32 void prop_sweep_kernel(PropK a, SweepK s) {
 
 template <int D, int UNROLL, int MODE, bool MASKED>
 static void launch_main(dim3 grid, hipStream_t st, const PropK &k) {
+  if constexpr (MODE != MIREC_IN_NONE) {
+    if (k.val != nullptr) {
+      constexpr int MW = MODE | kWeighted;
+      if (k.row_mask != nullptr)
+        hipLaunchKernelGGL((prop_kernel<D, UNROLL, MW, MASKED, true>), grid, dim3(256), 0, st, k);
+      else
+        hipLaunchKernelGGL((prop_kernel<D, UNROLL, MW, MASKED, false>), grid, dim3(256), 0, st, k);
+      return;
+    }
+  }
   if (k.row_mask != nullptr)
     hipLaunchKernelGGL((prop_kernel<D, UNROLL, MODE, MASKED, true>), grid, dim3(256), 0, st, k);
   else
@@ -667,6 +706,92 @@ __global__ __launch_bounds__(256) void prescale_kernel(const float *__restrict__
     st4(out + 4 * i, f4_scale(dinv[i / d4], ld4(x + 4 * i)));
 }
 
+// ---- per-entry dot (mirec_edge_dot): out[e] = <a[row(e)], b[col[e]]> for
+// every CSR entry, the gradient of y = A x with respect to the entry values
+// (a = dL/dy, b = x).  Balanced by ENTRIES: a wave owns kDotChunk consecutive
+// entries whatever rows they belong to, so a hub row is spread over many
+// waves and no wave's work depends on the maximum degree.  The rows of the
+// chunk's first and last entries are found by binary search in rowptr (the
+// last row r with rowptr[r] <= e: empty rows are stepped over); a lane then
+// finds the row of its own entry inside that range, which is a single row
+// for a chunk inside a hub.  Like gather_rows, 64 columns are read per
+// coalesced load and broadcast; an LPR-lane group takes one entry at a time
+// (one float4 of each row per lane), reduces the products inside the group
+// and hands the sum to the lane that holds the entry, so the 64 results are
+// stored coalesced.  Every entry is written once; no atomics.
+constexpr int kDotChunk = 256;
+
+__device__ __forceinline__ int32_t row_of_entry(const int64_t *rowptr, int32_t lo, int32_t hi,
+                                                int64_t e) {
+  while (lo < hi) {  // invariant: rowptr[lo] <= e, the answer lies in [lo, hi]
+    const int32_t mid = lo + (hi - lo + 1) / 2;
+    if (rowptr[mid] <= e)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  return lo;
+}
+
+template <int D, int UNROLL>
+__global__ __launch_bounds__(256) MIREC_NO_PK_F32 void edge_dot_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, int64_t n_rows,
+    int64_t nnz, const float *__restrict__ a, const float *__restrict__ b,
+    float *__restrict__ out) {
+  constexpr int LPR = D / 4;
+  constexpr int G = 64 / LPR;
+  const int lane = threadIdx.x & 63;
+  const int grp = lane / LPR;
+  const int sub = lane % LPR;
+  const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t e0 = wave * kDotChunk;
+  if (e0 >= nnz) return;  // wave-uniform
+  const int64_t e1 = min(e0 + (int64_t)kDotChunk, nnz);
+  const int32_t r_lo = row_of_entry(rowptr, 0, (int32_t)(n_rows - 1), e0);
+  const int32_t r_hi = row_of_entry(rowptr, r_lo, (int32_t)(n_rows - 1), e1 - 1);
+  for (int64_t base = e0; base < e1; base += 64) {
+    const int cnt = (int)min((int64_t)64, e1 - base);
+    const int myc = lane < cnt ? col[base + lane] : 0;
+    const int myrow = lane < cnt ? row_of_entry(rowptr, r_lo, r_hi, base + lane) : r_lo;
+    float res = 0.f;
+    for (int k = 0; k < cnt; k += G * UNROLL) {
+      float4 va[UNROLL], vb[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const int idx = k + u * G + grp;
+        const int j = __shfl(myc, idx & 63);
+        const int r = __shfl(myrow, idx & 63);
+        if (idx < cnt) {
+          va[u] = ld4(a + (int64_t)r * D + sub * 4);
+          vb[u] = ld4(b + (int64_t)j * D + sub * 4);
+        } else {
+          va[u] = f4_zero();
+          vb[u] = f4_zero();
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const float d = group_sum<LPR>(f4_dot(va[u], vb[u]));
+        // entry k + u*G + g was summed by group g: lane k + u*G + g takes it
+        const float t = __shfl(d, (lane & (G - 1)) * LPR);
+        if (lane >= k + u * G && lane < k + (u + 1) * G) res = t;
+      }
+    }
+    if (lane < cnt) out[base + lane] = res;
+  }
+}
+
+template <int D, int UNROLL>
+static int launch_edge_dot(const mirec_csr_t *c, const float *a, const float *b, float *out,
+                           hipStream_t st) {
+  const int64_t waves = (c->nnz + kDotChunk - 1) / kDotChunk;
+  const int64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
+  hipLaunchKernelGGL((edge_dot_kernel<D, UNROLL>), dim3((unsigned)blocks), dim3(256), 0, st,
+                     c->rowptr, c->col, c->n_rows, c->nnz, a, b, out);
+  MIREC_LAUNCH_CHECK();
+  return MIREC_OK;
+}
+
 }  // namespace mirec
 
 namespace mirec {
@@ -676,6 +801,7 @@ namespace mirec {
 // the layout is built.
 static bool sweep_qualifies(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sweep_t *sw) {
   if (sw == nullptr || p->dim != 64) return false;
+  if (c->val != nullptr) return false;  // the sweep layout carries no values
   if (p->in_mode != MIREC_IN_PRESCALED) return false;
   if (p->in_mask != nullptr || p->row_mask != nullptr || p->row_list != nullptr) return false;
   if (c->n_seg > 0) return false;
@@ -782,6 +908,7 @@ extern "C" int mirec_propagate_sweep(const mirec_csr_t *c, const mirec_prop_t *p
   k.narrow_max = p->narrow_max;
   k.wide_list = p->wide_list;
   k.wide_count = p->wide_count;
+  k.val = c->val;
   const int64_t cap = p->row_list_cap;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (sweep_qualifies(c, p, sw)) return launch_sweep<64, 4>(c, k, sw, st);
@@ -793,6 +920,27 @@ extern "C" int mirec_propagate_sweep(const mirec_csr_t *c, const mirec_prop_t *p
     case 64: return launch_prop<64, 4>(c, k, cap, p->in_mode, st);
     case 128: return launch_prop<128, 4>(c, k, cap, p->in_mode, st);
     case 256: return launch_prop<256, 8>(c, k, cap, p->in_mode, st);
+  }
+  return MIREC_ERR_DIM;
+}
+
+extern "C" int mirec_edge_dot(const mirec_csr_t *c, const float *a, const float *b, int32_t dim,
+                              float *out, mirec_stream_t stream) {
+  using namespace mirec;
+  MIREC_CHECK_ARG(c != nullptr && c->rowptr != nullptr && c->n_rows >= 0 && c->nnz >= 0);
+  if (!dim_supported(dim)) return MIREC_ERR_DIM;
+  if (c->nnz == 0) return MIREC_OK;
+  MIREC_CHECK_ARG(c->n_rows > 0 && c->col != nullptr && a != nullptr && b != nullptr &&
+                  out != nullptr);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  switch (dim) {
+    case 4: return launch_edge_dot<4, 1>(c, a, b, out, st);
+    case 8: return launch_edge_dot<8, 1>(c, a, b, out, st);
+    case 16: return launch_edge_dot<16, 1>(c, a, b, out, st);
+    case 32: return launch_edge_dot<32, 2>(c, a, b, out, st);
+    case 64: return launch_edge_dot<64, 4>(c, a, b, out, st);
+    case 128: return launch_edge_dot<128, 4>(c, a, b, out, st);
+    case 256: return launch_edge_dot<256, 4>(c, a, b, out, st);
   }
   return MIREC_ERR_DIM;
 }

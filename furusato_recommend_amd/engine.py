@@ -45,7 +45,7 @@ from .graph import Graph
 
 
 def prop_launch_bytes(in_mode: int, n_nodes: int, nnz: int, dim: int, *, slot=False,
-                      xs_out=False, addend=False, out=False, adam=False) -> int:
+                      xs_out=False, addend=False, out=False, adam=False, weighted=False) -> int:
     """Algorithmic HBM bytes of one mirec_propagate launch:
     every operand the launch must read or write, each exactly once."""
     N, D = n_nodes, dim
@@ -57,6 +57,8 @@ def prop_launch_bytes(in_mode: int, n_nodes: int, nnz: int, dim: int, *, slot=Fa
         b += nnz * (D * 4 + 4 + 4)                # + dinv_j per entry
     elif in_mode == IN_SPARSE:
         b += nnz * (4 + 4 + 4)                    # col, dinv_j, slot_j
+    if weighted and in_mode != IN_NONE:
+        b += nnz * 4                              # the per-entry edge weight
     if slot:
         b += N * 4                                # slot_i
     b += row * (int(xs_out) + int(addend) + int(out))
@@ -279,7 +281,9 @@ class PropagationEngine:
         self.use_hop_list = True      # F1 launches walk hop_list (else: byte map)
         self.reuse_prescaled = True   # fused update writes the next x~_0
         # full PRESCALED launches gather the item rows with the column sweep
-        # (graphs that qualify, Graph.sweep_layout; else the row kernel)
+        # (graphs that qualify, Graph.sweep_layout; else the row kernel; an
+        # edge-weighted graph never does: every launch below then runs the
+        # weighted row kernel, csr.val carried by the graph)
         self.use_sweep = True
         self.sweep = graph.sweep_layout(self.dim)
         # first backward layer's neighbour filter: "slot" (one dependent load;
@@ -383,7 +387,8 @@ class PropagationEngine:
         return prop_launch_bytes(p.in_mode, g.n_nodes, g.nnz, self.dim,
                                  slot=bool(p.slot and (p.seed or p.seed2)),
                                  xs_out=bool(p.xs_out), addend=bool(p.addend) and not om,
-                                 out=bool(p.out) and not om, adam=bool(p.param))
+                                 out=bool(p.out) and not om, adam=bool(p.param),
+                                 weighted=g.val is not None)
 
     def compute_frontier(self, users=None, pos=None, neg=None, keys=None, n_keys: int = 0):
         """bm_self = S, bm_hop = S ∪ N(S) for a triple batch or a key list;
@@ -744,9 +749,26 @@ class PropagationEngine:
         return loss
 
 
+def edge_dot(graph: Graph, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor):
+    """out[k] = <a[row(k)], b[col[k]]> for every CSR entry k of ``graph``
+    (mirec_edge_dot; a, b: contiguous fp32 [n_nodes, D], D in SUPPORTED_DIMS,
+    out: fp32 [nnz])."""
+    n, D = a.shape
+    if D not in _lib.SUPPORTED_DIMS or n != graph.n_nodes or b.shape != a.shape:
+        raise ValueError(f"edge_dot: a {tuple(a.shape)}, b {tuple(b.shape)}, "
+                         f"graph of {graph.n_nodes} nodes")
+    if (a.dtype != torch.float32 or b.dtype != torch.float32 or out.dtype != torch.float32
+            or not (a.is_contiguous() and b.is_contiguous() and out.is_contiguous())
+            or out.numel() < graph.nnz):
+        raise ValueError("edge_dot: contiguous float32 tensors, out of nnz entries required")
+    check(lib.mirec_edge_dot(graph.csr_ptr(), a.data_ptr(), b.data_ptr(), D, out.data_ptr(),
+                             _lib.stream_handle()), "edge_dot")
+
+
 def propagate(graph: Graph, x: torch.Tensor, out: torch.Tensor):
     """out = Â x on ``graph`` (one LGConv call; x, out: contiguous fp32
-    [n_nodes, D] device tensors, D in SUPPORTED_DIMS)."""
+    [n_nodes, D] device tensors, D in SUPPORTED_DIMS; edge-weighted when the
+    graph carries values)."""
     n, D = x.shape
     if D not in _lib.SUPPORTED_DIMS or n != graph.n_nodes or out.shape != x.shape:
         raise ValueError(f"propagate: x {tuple(x.shape)}, out {tuple(out.shape)}, "

@@ -7,6 +7,13 @@ model/radj.py:28-36).  Here both are computed once: a destination-major CSR
 (int64 rowptr, int32 col, rows in the reference's edge order) and
 dinv = deg^-1/2, built on the host by libmirec (mirec_csr_bipartite) and
 kept in HBM for the lifetime of the model.
+
+Edge weights (optional): a per-edge float array makes the matrix
+A_ij = Σ w over the edges (j → i); the values live beside ``col`` in CSR
+order (``val = w[perm]``, ``perm`` = mirec_csr_entry_order) and the degree of
+gcn_norm becomes the sum of the weights into a node.  The samplers, the
+frontier, GraphSAGE and the data-parallel drivers read the same CSR and use
+its structure only: they ignore ``val``.
 """
 from __future__ import annotations
 
@@ -41,12 +48,49 @@ class SweepLayout:
         return ctypes.byref(self.desc)
 
 
+def _entry_order(dst: np.ndarray, n_nodes: int) -> np.ndarray:
+    """perm[k] = index in the edge list of CSR entry k (mirec_csr_from_coo's
+    stable order by destination)."""
+    dst = np.ascontiguousarray(dst, dtype=np.int64)
+    perm = np.empty(dst.shape[0], np.int64)
+    check(lib.mirec_csr_entry_order(dst.ctypes.data, dst.shape[0], int(n_nodes),
+                                    perm.ctypes.data), "csr_entry_order")
+    return perm
+
+
+def _check_weights(w, n_edges: int, normalize: bool, what: str) -> np.ndarray:
+    """Per-edge weights as a contiguous float32 host array (ValueError unless
+    one finite entry per edge, non-negative under gcn_norm)."""
+    if torch.is_tensor(w):
+        w = w.detach().cpu().numpy()
+    w = np.asarray(w)
+    if w.ndim != 1 or w.shape[0] != n_edges:
+        raise ValueError(f"{what}: one weight per edge ({n_edges}), got shape {tuple(w.shape)}")
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if not np.isfinite(w).all():
+        raise ValueError(f"{what}: weights must be finite")
+    if normalize and (w < 0).any():
+        raise ValueError(f"{what}: weights must be non-negative with normalize=True "
+                         "(deg^-1/2 of a weighted degree)")
+    return w
+
+
+def _weighted_dinv(dst: np.ndarray, w: np.ndarray, n_nodes: int) -> np.ndarray:
+    """gcn_norm(add_self_loops=False): deg_i = Σ of the weights into i, in
+    float64; dinv = deg^-1/2, 0 where deg == 0."""
+    deg = np.bincount(dst, weights=w.astype(np.float64), minlength=n_nodes)
+    # 1 / sqrt(deg) rounded to float32 like the unweighted fill: all-ones
+    # weights give the unweighted dinv bit for bit
+    return np.where(deg > 0, 1.0 / np.sqrt(np.where(deg > 0, deg, 1.0)), 0.0).astype(np.float32)
+
+
 class Graph:
     """CSR of the normalised adjacency Â = D^-1/2 A D^-1/2 (A symmetric)."""
 
     def __init__(self, rowptr: np.ndarray, col: np.ndarray, dinv: np.ndarray,
                  n_users: int, m_items: int, device, split: int = DEFAULT_SPLIT,
-                 symmetric: bool = True):
+                 symmetric: bool = True, val: np.ndarray | None = None,
+                 perm: np.ndarray | None = None, normalize: bool = True):
         self.n_users = int(n_users)
         self.m_items = int(m_items)
         self.n_nodes = int(rowptr.shape[0] - 1)
@@ -55,6 +99,7 @@ class Graph:
         self.device = torch.device(device)
         self.rowptr_host = rowptr
         self.col_host = col
+        self.dinv_host = dinv
         self.split = int(split)
         n_long, n_seg = ctypes.c_int64(0), ctypes.c_int64(0)
         check(lib.mirec_csr_long_rows(rowptr.ctypes.data, self.n_nodes, self.split,
@@ -85,7 +130,17 @@ class Graph:
                        long_rows=self.long_rows.data_ptr(),
                        long_segptr=self.long_segptr.data_ptr(),
                        seg_row=self.seg_row.data_ptr(), seg_beg=self.seg_beg.data_ptr(),
-                       col_sorted=None, n_sorted=0)
+                       col_sorted=None, n_sorted=0, val=None)
+        # edge weights: val[k] = w[perm[k]] in CSR order (None = all ones);
+        # perm stays on the device for set_edge_weight
+        self.normalize = bool(normalize)
+        self.val = self.perm = None
+        self._coo = None       # host (src, dst) of a from_edge_index graph
+        self._w_token = None   # the weight tensor `val` was last refreshed from
+        if val is not None:
+            self.val = torch.from_numpy(val if val.size else np.zeros(1, np.float32)).to(dev)
+            self.perm = torch.from_numpy(perm).to(dev)
+            self.csr.val = self.val.data_ptr()
         self.transpose = None  # set for non-symmetric graphs (from_edge_index)
         self.col_sorted = None
         self.pos_cdf = None  # weighted positives (set_positive_probs)
@@ -107,8 +162,10 @@ class Graph:
     # ------------------------------------------------------------------ build
     @classmethod
     def from_interactions(cls, train_user, train_item, n_users: int, m_items: int,
-                          device, split: int = DEFAULT_SPLIT) -> "Graph":
-        """trainUser / trainItem arrays (dataloader.py:93-124) → symmetric CSR."""
+                          device, split: int = DEFAULT_SPLIT, weight=None) -> "Graph":
+        """trainUser / trainItem arrays (dataloader.py:93-124) → symmetric CSR.
+        ``weight`` (one finite, non-negative value per interaction): both
+        directions of interaction e carry weight[e], degrees are weight sums."""
         u = np.ascontiguousarray(np.asarray(train_user, dtype=np.int64))
         i = np.ascontiguousarray(np.asarray(train_item, dtype=np.int64))
         if u.shape != i.shape:
@@ -120,17 +177,34 @@ class Graph:
         check(lib.mirec_csr_bipartite(u.ctypes.data, i.ctypes.data, u.shape[0], int(n_users),
                                       int(m_items), rowptr.ctypes.data, col.ctypes.data,
                                       dinv.ctypes.data), "csr_bipartite")
-        return cls(rowptr, col, dinv, n_users, m_items, device, split)
+        if weight is None:
+            return cls(rowptr, col, dinv, n_users, m_items, device, split)
+        ne = u.shape[0]
+        w = _check_weights(weight, ne, True, "from_interactions")
+        # the CSR is the stable destination sort of the reference's doubled
+        # edge list (user -> item, then item -> user); edge e of it is
+        # interaction e mod ne
+        dst2 = np.concatenate([i + int(n_users), u])
+        perm = _entry_order(dst2, n) % max(ne, 1)
+        dinv = _weighted_dinv(dst2, np.concatenate([w, w]), n)
+        return cls(rowptr, col, dinv, n_users, m_items, device, split, val=w[perm], perm=perm)
 
     @classmethod
     def from_edge_index(cls, edge_index, n_nodes: int, device,
-                        split: int = DEFAULT_SPLIT, normalize: bool = True) -> "Graph":
+                        split: int = DEFAULT_SPLIT, normalize: bool = True,
+                        edge_weight=None) -> "Graph":
         """Generic LGConv graph: edge_index[0] = source, [1] = target (PyG
         flow source_to_target; degree = in-degree at the target, multi-edges
-        counted).  ``normalize=False``: plain neighbour sum (dinv = 1)."""
+        counted).  ``normalize=False``: plain neighbour sum (dinv = 1).
+        ``edge_weight`` (one finite value per edge, non-negative with
+        ``normalize``): A_ij = Σ of the weights of the edges (j → i), each
+        duplicate edge its own entry; degree = Σ of the weights into the
+        target (PyG gcn_norm, add_self_loops=False)."""
         ei = np.ascontiguousarray(np.asarray(edge_index, dtype=np.int64))
         src, dst = np.ascontiguousarray(ei[0]), np.ascontiguousarray(ei[1])
         nnz = src.shape[0]
+        w = None if edge_weight is None else _check_weights(edge_weight, nnz, normalize,
+                                                            "from_edge_index")
         rowptr = np.empty(n_nodes + 1, np.int64)
         col = np.empty(nnz, np.int32)
         dinv = np.empty(n_nodes, np.float32)
@@ -139,26 +213,77 @@ class Graph:
               "csr_from_coo")
         if not normalize:
             dinv[:] = 1.0
+        elif w is not None:
+            dinv = _weighted_dinv(dst, w, n_nodes)
         # Is the edge multiset symmetric?  Then Âᵀ = Â (same CSR for backward).
-        fwd = np.sort(src * n_nodes + dst)
-        bwd = np.sort(dst * n_nodes + src)
-        symmetric = bool(np.array_equal(fwd, bwd))
-        g = cls(rowptr, col, dinv, n_nodes, 0, device, split, symmetric=symmetric)
+        # With weights: the multiset of (src, dst, weight) triples.
+        kf, kb = src * n_nodes + dst, dst * n_nodes + src
+        if w is None:
+            symmetric = bool(np.array_equal(np.sort(kf), np.sort(kb)))
+            g = cls(rowptr, col, dinv, n_nodes, 0, device, split, symmetric=symmetric,
+                    normalize=normalize)
+        else:
+            of, ob = np.lexsort((w, kf)), np.lexsort((w, kb))
+            symmetric = bool(np.array_equal(kf[of], kb[ob]) and np.array_equal(w[of], w[ob]))
+            perm = _entry_order(dst, n_nodes)
+            g = cls(rowptr, col, dinv, n_nodes, 0, device, split, symmetric=symmetric,
+                    val=w[perm], perm=perm, normalize=normalize)
+        g._coo = (src, dst)
         if not symmetric:
-            # Backward of y = Â x is x̄ = Âᵀ ȳ: CSR by source, same dinv.
-            rowptr_t = np.empty(n_nodes + 1, np.int64)
-            col_t = np.empty(nnz, np.int32)
-            check(lib.mirec_csr_from_coo(dst.ctypes.data, src.ctypes.data, nnz, n_nodes,
-                                         rowptr_t.ctypes.data, col_t.ctypes.data, None),
-                  "csr_from_coo(transpose)")
-            g.transpose = cls(rowptr_t, col_t, dinv, n_nodes, 0, device, split)
+            g._build_transpose(w)
         return g
+
+    def _build_transpose(self, w: np.ndarray | None):
+        """Backward of y = Â x is x̄ = Âᵀ ȳ: CSR by source, same dinv, the
+        values permuted into its own entry order."""
+        src, dst = self._coo
+        n_nodes, nnz = self.n_nodes, src.shape[0]
+        rowptr_t = np.empty(n_nodes + 1, np.int64)
+        col_t = np.empty(nnz, np.int32)
+        check(lib.mirec_csr_from_coo(dst.ctypes.data, src.ctypes.data, nnz, n_nodes,
+                                     rowptr_t.ctypes.data, col_t.ctypes.data, None),
+              "csr_from_coo(transpose)")
+        kw = {}
+        if w is not None:
+            perm_t = _entry_order(src, n_nodes)
+            kw = dict(val=w[perm_t], perm=perm_t)
+        self.transpose = Graph(rowptr_t, col_t, self.dinv_host, n_nodes, 0, self.device,
+                               self.split, normalize=self.normalize, **kw)
+
+    def set_edge_weight(self, w: torch.Tensor) -> None:
+        """Refresh the values of a weighted ``normalize=False`` graph from a
+        device tensor of per-edge weights (edge order of the build): one
+        gather through ``perm`` on the current stream, no host sync and no
+        rebuild (dinv = 1 does not depend on the weights).  Nothing here can
+        look at the new values, so a from_edge_index graph that was symmetric
+        for its first weights gets its transpose now (once, host work on the
+        structure only) and is treated as non-symmetric from then on."""
+        if self.val is None:
+            raise ValueError("set_edge_weight: the graph was built without edge weights")
+        if self.normalize:
+            raise ValueError("set_edge_weight: dinv of a normalize=True graph depends on the "
+                             "weights; rebuild the graph instead")
+        n_edges = self.nnz // 2 if self._coo is None else self.nnz
+        if w.dim() != 1 or w.shape[0] != n_edges:
+            raise ValueError(f"set_edge_weight: one weight per edge ({n_edges}), "
+                             f"got shape {tuple(w.shape)}")
+        w = w.detach().to(device=self.device, dtype=torch.float32)
+        if self.nnz:
+            torch.index_select(w, 0, self.perm, out=self.val[: self.nnz])
+        if self._coo is not None:
+            if self.transpose is None:
+                self._build_transpose(np.zeros(self.nnz, np.float32))
+                self.symmetric = False
+            t = self.transpose
+            if self.nnz:
+                torch.index_select(w, 0, t.perm, out=t.val[: self.nnz])
+        self._w_token = None
 
     # ------------------------------------------------------------ column sweep
     def sweep_layout(self, dim: int, tile_rows: int | None = None,
                      group_rows: int | None = None, band_rows: int | None = None):
         """The column-ordered layout of the item rows (mirec_sweep_t) for
-        width ``dim``, or None when the graph does not qualify: not a
+        width ``dim``, or None when the graph does not qualify: edge weights, not a
         bipartite user–item graph, a long row anywhere (n_seg > 0), no sweep
         kernel for the width; and, with the default sizes, fewer item rows
         than CUs or a user block that fits one XCD's L2.  Defaults: two tiles
@@ -174,6 +299,8 @@ class Graph:
 
     def _build_sweep(self, dim, tile_rows, group_rows, band_rows):
         nu, mi = self.n_users, self.m_items
+        if self.val is not None:  # the sweep layout carries no values
+            return None
         max_groups = int(lib.mirec_sweep_groups(dim))
         if not (self.symmetric and nu > 0 and mi > 0 and nu + mi == self.n_nodes):
             return None
@@ -271,6 +398,8 @@ class Graph:
         """Algorithmic HBM bytes of one propagation layer."""
         n, nnz = self.n_nodes, self.nnz
         b = nnz * dim * 4 + nnz * 4 + (n + 1) * 8 + n * 4 + n * dim * 4
+        if self.val is not None:
+            b += nnz * 4  # the per-entry weight
         if fused_acc:
             b += 2 * n * dim * 4
         return b

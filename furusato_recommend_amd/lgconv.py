@@ -11,6 +11,16 @@ transposed CSR (the same CSR when the edge multiset is symmetric).  The call
 goes through the registered operator ``torch.ops.mirec.lgcn_propagate``
 (ops.py).
 
+``edge_weight`` (PyG's third argument, one float per edge): A_ij = Σ of the
+weights of the edges (j → i) and, with ``normalize``, PyG's
+gcn_norm(add_self_loops=False) on the weighted in-degree.  The call goes
+through ``torch.ops.mirec.lgcn_propagate_w``; with ``normalize=False`` the
+weights may require grad (the gradient is the per-edge dot kernel,
+mirec_edge_dot) and may change from call to call (the CSR values are
+refreshed on the device, no rebuild); with ``normalize=True`` they are static
+data: a changed weight tensor rebuilds dinv on the host, and a weight that
+requires grad raises NotImplementedError.
+
 The CSR (and its transpose) is built once per ``edge_index`` and cached on
 the module, keyed by the tensor's storage, shape and version; ``x`` may
 have any feature width: widths outside {4, 8, ..., 256} are zero-padded to
@@ -73,27 +83,46 @@ class LGConv(nn.Module):
         self._key = None
         self._graph = None
 
-    def graph_for(self, edge_index: torch.Tensor, n_nodes: int, device) -> Graph:
+    def graph_for(self, edge_index: torch.Tensor, n_nodes: int, device,
+                  edge_weight: torch.Tensor | None = None) -> Graph:
         key = (edge_index.data_ptr(), tuple(edge_index.shape), edge_index._version,
-               int(n_nodes), str(device))
+               int(n_nodes), str(device), edge_weight is not None)
+        if edge_weight is not None and self.normalize:
+            # dinv depends on the weights: they are part of the graph
+            key += (edge_weight.data_ptr(), edge_weight._version)
         if self._key != key:
             kw = {} if self.split is None else {"split": int(self.split)}
+            if edge_weight is not None:
+                kw["edge_weight"] = edge_weight.detach().cpu().numpy()
             self._graph = Graph.from_edge_index(edge_index.detach().cpu().numpy(), int(n_nodes),
                                                 device, normalize=self.normalize, **kw)
+            # (the key's pointers stay valid: the graph keeps the weight tensor)
+            self._graph._key_refs = (edge_index, edge_weight)
             self._key = key
         return self._graph
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor,
                 edge_weight: torch.Tensor | None = None) -> torch.Tensor:
-        if edge_weight is not None:
-            raise NotImplementedError("LGConv: edge_weight is not supported")
         if x.device.type != "cuda":
             raise RuntimeError("LGConv (furusato_recommend_amd) runs on a HIP device only")
         if x.dim() != 2 or x.dtype != torch.float32:
             raise ValueError("LGConv: x must be a float32 [N, D] tensor")
-        g = self.graph_for(edge_index, x.shape[0], x.device)
-        from .ops import handle  # torch.ops.mirec.lgcn_propagate (autograd registered)
-        return torch.ops.mirec.lgcn_propagate(x, handle(g))
+        from .ops import handle  # torch.ops.mirec.lgcn_propagate* (autograd registered)
+        if edge_weight is None:
+            g = self.graph_for(edge_index, x.shape[0], x.device)
+            return torch.ops.mirec.lgcn_propagate(x, handle(g))
+        if (edge_weight.dim() != 1 or edge_weight.shape[0] != edge_index.shape[1]
+                or not edge_weight.is_floating_point()):
+            raise ValueError(f"LGConv: edge_weight must be a float [{edge_index.shape[1]}] "
+                             f"tensor (one per edge), got {edge_weight.dtype} "
+                             f"{tuple(edge_weight.shape)}")
+        if self.normalize and edge_weight.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError(
+                "LGConv: the gradient with respect to edge_weight is not implemented for "
+                "normalize=True (dinv depends on the weights); use normalize=False or "
+                "detach the weights")
+        g = self.graph_for(edge_index, x.shape[0], x.device, edge_weight)
+        return torch.ops.mirec.lgcn_propagate_w(x, edge_weight.to(x.device), handle(g))
 
     def __repr__(self) -> str:
         return f"LGConv(normalize={self.normalize})"

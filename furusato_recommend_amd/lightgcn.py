@@ -67,9 +67,20 @@ class LightGCN(nn.Module):
         self.device = torch.device(config.get("device", "cuda:0"))
         if self.device.type != "cuda":
             raise RuntimeError("LightGCN (furusato_recommend_amd) runs on a HIP device only")
+        # config["edge_weight"]: one non-negative weight per training
+        # interaction, aligned with dataset.trainUser / trainItem (counts,
+        # recency decay, confidence); None = the plain 0/1 graph.  Every path
+        # below (stageOne, OneEpoch, forward, getUsersRating, the streamed
+        # evaluation, frontier pruning, the fused Adam) then runs weighted:
+        # the weights live in the graph's CSR.
+        weight = config.get("edge_weight")
+        if weight is not None and len(weight) != len(dataset.trainUser):
+            raise ValueError(f"config['edge_weight']: {len(weight)} weights for "
+                             f"{len(dataset.trainUser)} training interactions")
         self.graph = Graph.from_interactions(dataset.trainUser, dataset.trainItem,
                                              self.num_users, self.num_items, self.device,
-                                             split=int(config.get("csr_split", DEFAULT_SPLIT)))
+                                             split=int(config.get("csr_split", DEFAULT_SPLIT)),
+                                             weight=weight)
         self.graph.set_positive_probs(positive_probs(config))
         self.__init_weight()
         self.optim = AdamState(self.all_embedding.weight, lr=config["lr"])

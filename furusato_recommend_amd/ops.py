@@ -16,8 +16,13 @@ call's backward, would otherwise drop the only other reference).
     y.backward(g)                                      # x.grad = Âᵀ g
 
 ``lgcn_propagate_t`` is Âᵀ x (the same CSR for a symmetric edge multiset,
-the transposed one otherwise).  Both have fake (meta) implementations, so
-they trace under torch.compile / torch.export without running a kernel.
+the transposed one otherwise).  ``lgcn_propagate_w(x, edge_weight, graph)`` is
+the edge-weighted y = Â x on a graph built with weights
+(``Graph.from_edge_index(..., edge_weight=)``): its backward gives Âᵀ ȳ for
+``x`` and, on a ``normalize=False`` graph, the per-edge dots
+ȳ[dst_e] · x[src_e] (mirec_edge_dot) for ``edge_weight``.  All have fake
+(meta) implementations, so they trace under torch.compile / torch.export
+without running a kernel.
 Reference call sites: model/lgcn.py:66,82 (``LGConv()(x, edge_index)``).
 """
 from __future__ import annotations
@@ -80,6 +85,105 @@ def _(x, graph):
     return torch.empty_like(x)
 
 
+# ---- edge-weighted propagation ------------------------------------------------
+def _install(g, w: torch.Tensor) -> None:
+    """Make the normalize=False graph ``g`` hold the weights ``w``.  The graph
+    keeps the tensor it was last refreshed from (so its storage cannot be
+    reused by another tensor) and its version: the same tensor, unchanged,
+    costs nothing."""
+    tok = g._w_token
+    if (tok is not None and tok[0].data_ptr() == w.data_ptr() and tok[1] == w._version
+            and tok[0].shape == w.shape):
+        return
+    g.set_edge_weight(w)
+    g._w_token = (w.detach(), w._version)
+
+
+def _check_w(g, w: torch.Tensor) -> None:
+    if g.val is None:
+        raise ValueError("mirec.lgcn_propagate_w: the graph was built without edge weights")
+    n_edges = g.nnz // 2 if g._coo is None else g.nnz
+    if w.dim() != 1 or w.shape[0] != n_edges or not w.is_floating_point():
+        raise ValueError(f"mirec.lgcn_propagate_w: edge_weight must be a float [{n_edges}] "
+                         f"tensor, got {w.dtype} {tuple(w.shape)}")
+
+
+@torch.library.custom_op("mirec::lgcn_propagate_w", mutates_args=())
+def lgcn_propagate_w(x: torch.Tensor, edge_weight: torch.Tensor, graph: int) -> torch.Tensor:
+    """y = Â x with per-edge weights (csrc/prop.hip, the weighted prop_kernel instantiations).  On a
+    ``normalize=False`` graph ``edge_weight`` is installed into the graph's
+    CSR values first (a device gather, skipped when it already holds them); a
+    ``normalize=True`` graph is static: it holds the weights it was built
+    with (its dinv depends on them) and ``edge_weight`` must be those."""
+    g = _graph(graph)
+    _check_w(g, edge_weight)
+    if not g.normalize:
+        _install(g, edge_weight)
+    return _apply(g, x)
+
+
+@lgcn_propagate_w.register_fake
+def _(x, edge_weight, graph):
+    return torch.empty_like(x)
+
+
+def _edge_dot(g, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Per-entry dots in CSR order for any width (padding / 256-column blocks
+    like lgconv._spmm; the blocks' dots are added in column order)."""
+    import torch.nn.functional as F
+
+    from . import _lib
+    from .engine import edge_dot
+    from .lgconv import _width
+    out = torch.empty(max(g.nnz, 1), dtype=torch.float32, device=a.device)
+    d = a.shape[1]
+    if d in _lib.SUPPORTED_DIMS:
+        edge_dot(g, a.contiguous(), b.contiguous(), out)
+        return out[: g.nnz]
+    total = None
+    for c0 in range(0, d, 256):
+        ab, bb = a[:, c0:c0 + 256], b[:, c0:c0 + 256]
+        pad = _width(ab.shape[1]) - ab.shape[1]
+        edge_dot(g, F.pad(ab, (0, pad)).contiguous(), F.pad(bb, (0, pad)).contiguous(), out)
+        total = out.clone() if total is None else total.add_(out)
+    return total[: g.nnz]
+
+
+def _setup_w(ctx, inputs, output):
+    x, w, h = inputs
+    g = _graph(h)
+    ctx.graph_obj = g
+    ctx.w_grad = bool(ctx.needs_input_grad[1])
+    if ctx.w_grad and g.normalize:
+        raise NotImplementedError(
+            "mirec.lgcn_propagate_w: the gradient with respect to edge_weight is not "
+            "implemented for normalize=True (dinv depends on the weights); use "
+            "normalize=False or detach the weights")
+    ctx.save_for_backward(x if ctx.w_grad else None, None if g.normalize else w)
+
+
+def _bwd_w(ctx, grad):
+    g = ctx.graph_obj
+    x, w = ctx.saved_tensors
+    grad = grad.contiguous()
+    if w is not None:
+        _install(g, w)  # this call's weights, if the graph holds others by now
+    gx = _apply(g if g.symmetric else g.transpose, grad) if ctx.needs_input_grad[0] else None
+    gw = None
+    if ctx.w_grad:
+        dots = _edge_dot(g, grad, x)  # CSR order
+        if g._coo is not None:        # perm is a permutation of the edges
+            gw = torch.empty_like(dots).index_copy_(0, g.perm, dots)
+        else:                         # bipartite: both directions of interaction e
+            gw = torch.zeros(g.nnz // 2, dtype=dots.dtype, device=dots.device)
+            gw.index_add_(0, g.perm, dots)
+        gw = gw.to(w.dtype)
+    return gx, gw, None
+
+
+lgcn_propagate_w.register_autograd(_bwd_w, setup_context=_setup_w)
+
+
 def _setup(ctx, inputs, output):
     ctx.graph_obj = _graph(inputs[1])  # strong reference for the node's lifetime
 
@@ -95,4 +199,4 @@ def _bwd_t(ctx, grad):
 lgcn_propagate.register_autograd(_bwd, setup_context=_setup)
 lgcn_propagate_t.register_autograd(_bwd_t, setup_context=_setup)
 
-__all__ = ["handle", "lgcn_propagate", "lgcn_propagate_t"]
+__all__ = ["handle", "lgcn_propagate", "lgcn_propagate_t", "lgcn_propagate_w"]

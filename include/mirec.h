@@ -35,6 +35,9 @@
 extern "C" {
 #endif
 
+/* Still 1: mirec_csr_t gained a trailing field (`val`, the per-entry edge
+ * weights) after the version was set; a binding checks its mirror of the
+ * struct with mirec_struct_sizes, and a NULL `val` is the earlier behaviour. */
 #define MIREC_ABI_VERSION 1
 
 enum mirec_status {
@@ -76,6 +79,16 @@ int mirec_csr_bipartite(const int64_t *train_user, const int64_t *train_item,
 int mirec_csr_from_coo(const int64_t *src, const int64_t *dst, int64_t nnz,
                        int64_t n_nodes, int64_t *rowptr, int32_t *col,
                        float *dinv);
+
+/* The entry order of mirec_csr_from_coo: perm[k] is the index in the COO
+ * list of CSR entry k (the stable sort of the edges by destination), so
+ * per-edge data w goes into CSR order as val[k] = w[perm[k]].  For
+ * mirec_csr_bipartite pass the doubled edge list's destinations
+ * (n_users + train_item, then train_user): edge e of the doubled list is
+ * interaction e mod n_edges.  perm: [nnz].  MIREC_ERR_RANGE for a
+ * destination outside [0, n_nodes). */
+int mirec_csr_entry_order(const int64_t *dst, int64_t nnz, int64_t n_nodes,
+                          int64_t *perm);
 
 /* Long-row schedule for load balance: rows with more than `split` entries
  * are cut into segments of `split` entries.  Call once with NULL outputs
@@ -122,6 +135,12 @@ typedef struct mirec_csr {
    * them (the user rows of a bipartite graph) */
   const int32_t *col_sorted;
   int64_t n_sorted;
+  /* appended (see MIREC_ABI_VERSION): the matrix is A_ij = sum of val over
+   * the entries (j -> i) instead of their count, and dinv comes from the
+   * weighted degree (the caller's choice: gcn_norm's sum of the weights into
+   * i, or all ones).  Read by mirec_propagate and mirec_edge_dot's callers
+   * only; samplers, frontier and GraphSAGE use the structure alone. */
+  const float *val; /* [nnz] per-entry weight, NULL = all ones */
 } mirec_csr_t;
 
 /* Host: rows [0, n_rows) of (rowptr, col) with each row sorted ascending into
@@ -152,6 +171,8 @@ typedef struct mirec_adam_hparams {
 
 /* For every row i of the CSR:
  *   y_i   = dinv_i * sum_{j in row i} xin~_j                (Â x, fp32)
+ *           with csr->val: sum_{e = (j -> i)} val_e * xin~_j, the terms in
+ *           the same (CSR) order; every in_mode, mask and row list applies
  *   z_i   = y_i + seed[slot_i]               (if seed != NULL and slot_i >= 0)
  *   xs_out_i = dinv_i * z_i                  (if xs_out != NULL; next layer)
  *   o_i   = (z_i + addend_i) / divisor + seed2[slot_i]
@@ -259,11 +280,20 @@ int mirec_sweep_groups(int32_t dim);
 /* mirec_propagate with the rows of `sw` gathered by the sweep kernel and the
  * rows [0, sw->row0) by the row kernel, on the same stream, when the launch
  * qualifies: in_mode PRESCALED, no in_mask / row_mask / row list, no long-row
- * segments (csr->n_seg == 0), sw->row0 + sw->n_rows == csr->n_rows and the
+ * segments (csr->n_seg == 0), no entry values (csr->val == NULL), sw->row0 + sw->n_rows == csr->n_rows and the
  * width has a sweep kernel.  Anything else (sw == NULL included) is exactly
  * mirec_propagate.  Per row the sum runs in ascending source column. */
 int mirec_propagate_sweep(const mirec_csr_t *csr, const mirec_prop_t *p,
                           const mirec_sweep_t *sw, mirec_stream_t stream);
+
+/* out[e] = sum_c a[row(e), c] * b[col[e], c] for every entry e of the CSR, in
+ * CSR order (row(e) = the row whose range holds e): with a = dL/dy and b = x
+ * the gradient of y = A x with respect to the entry values (csr->val itself
+ * and dinv are not read).  a: [n_rows, dim], b: [>= max col + 1, dim],
+ * out: [nnz].  Work is split by entries, not rows; every entry is written
+ * once, no atomics, a fixed summation order. */
+int mirec_edge_dot(const mirec_csr_t *csr, const float *a, const float *b,
+                   int32_t dim, float *out, mirec_stream_t stream);
 
 /* out = dinv ⊙ x row-wise (the pre-scaled layer-0 input x~_0). */
 int mirec_prescale(const float *x, const float *dinv, int64_t n_rows,
