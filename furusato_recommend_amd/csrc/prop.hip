@@ -84,127 +84,57 @@ constexpr int kWeighted = 4;
 
 __device__ __forceinline__ bool bit_set(const uint8_t *bm, int64_t i) { return bm[i] != 0; }
 
-__device__ __forceinline__ void adam_elem(float &p, float &m, float &v, float g,
-                                          const mirec_adam_hparams_t &h) {
-  // torch.optim.Adam single-tensor path (torch/optim/adam.py:457-547):
-  // exp_avg.lerp_(g, 1-b1); exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2);
-  // denom = sqrt(v)/sqrt(bc2) + eps; p.addcdiv_(m, denom, -lr/bc1) — the
-  // shared expression of every Adam kernel (common.h)
-  adam1(p, m, v, g, h);
-}
-
 // Sum of the input rows listed in col[beg, end) (pre-scaled / raw x dinv_j /
-// sparse seeds x dinv_j), restricted to in_mask when MASKED.  Returns this
-// lane's group partial (a disjoint subset of the neighbours).
+// sparse seeds x dinv_j), restricted to in_mask when MASKED.  One walk in two
+// shapes: the lanes that share a row read its entries W at a time (one
+// coalesced col load per chunk), filter and compact them, and broadcast them
+// to gather UNROLL float4 row loads per lane at a time.
+//   !NARROW  the whole wave walks one row: W = 64, the G lane groups take
+//            disjoint neighbours of a chunk (G x UNROLL rows in flight) and
+//            the caller adds their partials (combine_groups);
+//   NARROW   each LPR-lane group walks a row of its own: W = LPR, control flow
+//            is group-uniform and shuffles stay inside the group.  G rows
+//            progress per wave, so latency-bound short rows get G x the
+//            memory-level parallelism of the wave-per-row shape, which would
+//            leave most of a 64-entry chunk empty.
+// Returns this lane's partial (!NARROW: a disjoint subset of the neighbours;
+// NARROW: its group's row sum).
 // WEIGHTED: entry e's term is multiplied by val[e]; the value is loaded next
 // to its column and follows it through the compaction, and the per-neighbour
 // weight becomes val (PRESCALED, which then takes the fma form) or
 // val * dinv_j (RAW, SPARSE).  Same order of terms as the unweighted sum.
-template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED>
-__device__ __forceinline__ float4 gather_rows(const PropK &a, int64_t beg, int64_t end,
-                                              int lane) {
+template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED, bool NARROW>
+__device__ __forceinline__ float4 gather(const PropK &a, int64_t beg, int64_t end, int lane) {
   constexpr int LPR = D / 4;
   constexpr int G = 64 / LPR;
+  constexpr int W = NARROW ? LPR : 64;  // entries per chunk = lanes sharing it
   const int grp = lane / LPR;
   const int sub = lane % LPR;
+  const int l0 = NARROW ? grp * LPR : 0;  // first of the lanes sharing the chunk
+  const int me = NARROW ? sub : lane;     // this lane's position among them
   float4 acc = f4_zero();
   if (MODE == MIREC_IN_NONE) return acc;
   const float *src = (MODE == MIREC_IN_SPARSE) ? a.seed_in : a.x_in;
-  for (int64_t base = beg; base < end; base += 64) {
-    int cnt = (int)min((int64_t)64, end - base);
-    int myc = lane < cnt ? a.col[base + lane] : 0;
+  for (int64_t base = beg; base < end; base += W) {
+    int cnt = (int)min((int64_t)W, end - base);
+    int myc = me < cnt ? a.col[base + me] : 0;
     float myv = 1.f;
-    if constexpr (WEIGHTED) myv = lane < cnt ? a.val[base + lane] : 0.f;
+    if constexpr (WEIGHTED) myv = me < cnt ? a.val[base + me] : 0.f;
     // SPARSE: the seed-row slot itself is the filter (slot >= 0 <=> node in
     // S), one dependent load less than a byte-map test followed by the slot
     // (with an in_mask, SPARSE tests the byte map first and reads the slot
     // of the hits only: fewer slot reads when many neighbours are seeded)
     const bool slot_filter = MODE == MIREC_IN_SPARSE && a.in_mask == nullptr;
-    int myr = slot_filter ? (lane < cnt ? a.slot[myc] : -1) : myc;
+    int myr = slot_filter ? (me < cnt ? a.slot[myc] : -1) : myc;
     if (MASKED) {
-      const bool ok = lane < cnt && (slot_filter ? myr >= 0 : bit_set(a.in_mask, myc));
-      const unsigned long long m = __ballot(ok);
-      const int nv = __popcll(m);
-      if (nv == 0) continue;  // wave-uniform
-      if (nv < cnt) {
-        const int below = __popcll(m & ((1ull << lane) - 1ull));
-        const int dst = ok ? below : nv + (lane - below);
-        myc = __builtin_amdgcn_ds_permute(dst << 2, myc);
-        if (slot_filter) myr = __builtin_amdgcn_ds_permute(dst << 2, myr);
-        if (WEIGHTED)
-          myv = __int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int(myv)));
-      }
-      cnt = nv;
-    }
-    if (MODE != MIREC_IN_SPARSE) myr = myc;
-    else if (!slot_filter) myr = lane < cnt ? a.slot[myc] : 0;
-    float myw = 1.f;
-    if (MODE == MIREC_IN_RAW || MODE == MIREC_IN_SPARSE) {
-      if (lane < cnt) myw = a.dinv[myc];
-    }
-    if (WEIGHTED) myw = lane < cnt ? myv * myw : 0.f;
-    if (MODE == MIREC_IN_SPARSE && myr < 0) {  // byte map set without a seed row
-      myr = 0;
-      myw = 0.f;
-    }
-    for (int k = 0; k < cnt; k += G * UNROLL) {
-      float4 v[UNROLL];
-      float w[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int idx = k + u * G + grp;
-        const int j = __shfl(myr, idx & 63);
-        w[u] = (MODE != MIREC_IN_PRESCALED || WEIGHTED) ? __shfl(myw, idx & 63) : 1.f;
-        if (idx < cnt)
-          v[u] = ld4(src + (int64_t)j * D + sub * 4);
-        else
-          v[u] = f4_zero();
-      }
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        if (MODE != MIREC_IN_PRESCALED || WEIGHTED)
-          acc = f4_fma(w[u], v[u], acc);
-        else
-          acc = f4_add(acc, v[u]);
-      }
-    }
-  }
-  return acc;
-}
-
-// Group-per-row gather (short rows): each LPR-lane group owns one row and
-// walks its neighbours LPR at a time (one coalesced col load per chunk),
-// UNROLL float4 row loads in flight per lane.  G rows progress per wave, so
-// latency-bound short rows get G x the memory-level parallelism of the
-// wave-per-row path.  Control flow is group-uniform; shuffles stay inside
-// the group.
-template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED>
-__device__ __forceinline__ float4 gather_narrow(const PropK &a, int64_t beg, int64_t end,
-                                                int lane) {
-  constexpr int LPR = D / 4;
-  const int grp = lane / LPR;
-  const int sub = lane % LPR;
-  const int gbase = grp * LPR;
-  float4 acc = f4_zero();
-  if (MODE == MIREC_IN_NONE) return acc;
-  const float *src = (MODE == MIREC_IN_SPARSE) ? a.seed_in : a.x_in;
-  for (int64_t c = beg; c < end; c += LPR) {
-    int cnt = (int)min((int64_t)LPR, end - c);
-    int myc = sub < cnt ? a.col[c + sub] : 0;
-    float myv = 1.f;
-    if constexpr (WEIGHTED) myv = sub < cnt ? a.val[c + sub] : 0.f;
-    const bool slot_filter = MODE == MIREC_IN_SPARSE && a.in_mask == nullptr;
-    int myr = slot_filter ? (sub < cnt ? a.slot[myc] : -1) : myc;
-    if (MASKED) {
-      const bool ok = sub < cnt && (slot_filter ? myr >= 0 : bit_set(a.in_mask, myc));
+      const bool ok = me < cnt && (slot_filter ? myr >= 0 : bit_set(a.in_mask, myc));
       const unsigned long long bal = __ballot(ok);
-      const unsigned long long gm =
-          (LPR == 64) ? bal : ((bal >> gbase) & ((1ull << LPR) - 1ull));
-      const int nv = __popcll(gm);
-      if (nv == 0) continue;  // group-uniform
-      if (nv < cnt) {
-        const int below = __popcll(gm & ((1ull << sub) - 1ull));
-        const int dst = gbase + (ok ? below : nv + (sub - below));
+      const unsigned long long m = (W == 64) ? bal : ((bal >> l0) & ((1ull << W) - 1ull));
+      const int nv = __popcll(m);
+      if (nv == 0) continue;  // uniform over the lanes sharing the chunk
+      if (nv < cnt) {  // compact the valid entries to the front
+        const int below = __popcll(m & ((1ull << me) - 1ull));
+        const int dst = l0 + (ok ? below : nv + (me - below));
         myc = __builtin_amdgcn_ds_permute(dst << 2, myc);
         if (slot_filter) myr = __builtin_amdgcn_ds_permute(dst << 2, myr);
         if (WEIGHTED)
@@ -213,23 +143,23 @@ __device__ __forceinline__ float4 gather_narrow(const PropK &a, int64_t beg, int
       cnt = nv;
     }
     if (MODE != MIREC_IN_SPARSE) myr = myc;
-    else if (!slot_filter) myr = sub < cnt ? a.slot[myc] : 0;
+    else if (!slot_filter) myr = me < cnt ? a.slot[myc] : 0;
     float myw = 1.f;
     if (MODE == MIREC_IN_RAW || MODE == MIREC_IN_SPARSE) {
-      if (sub < cnt) myw = a.dinv[myc];
+      if (me < cnt) myw = a.dinv[myc];
     }
-    if (WEIGHTED) myw = sub < cnt ? myv * myw : 0.f;
+    if (WEIGHTED) myw = me < cnt ? myv * myw : 0.f;
     if (MODE == MIREC_IN_SPARSE && myr < 0) {  // byte map set without a seed row
       myr = 0;
       myw = 0.f;
     }
-    for (int k = 0; k < cnt; k += UNROLL) {
+    for (int k = 0; k < cnt; k += (NARROW ? 1 : G) * UNROLL) {
       float4 v[UNROLL];
       float w[UNROLL];
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
-        const int idx = k + u;
-        const int srcl = gbase + (idx & (LPR - 1));
+        const int idx = NARROW ? k + u : k + u * G + grp;
+        const int srcl = l0 + (idx & (W - 1));
         const int j = __shfl(myr, srcl);
         w[u] = (MODE != MIREC_IN_PRESCALED || WEIGHTED) ? __shfl(myw, srcl) : 1.f;
         if (idx < cnt)
@@ -275,10 +205,14 @@ __device__ __forceinline__ void row_epilogue(const PropK &a, int64_t row, float4
   if (a.seed2 != nullptr && sl >= 0) o = f4_add(o, ld4(a.seed2 + (int64_t)sl * D + sub * 4));
   if (a.param != nullptr) {
     float4 p = ld4(a.param + off), m = ld4(a.m + off), v = ld4(a.v + off);
-    adam_elem(p.x, m.x, v.x, o.x, a.adam);
-    adam_elem(p.y, m.y, v.y, o.y, a.adam);
-    adam_elem(p.z, m.z, v.z, o.z, a.adam);
-    adam_elem(p.w, m.w, v.w, o.w, a.adam);
+    // torch.optim.Adam single-tensor path (torch/optim/adam.py:457-547):
+    // exp_avg.lerp_(g, 1-b1); exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2);
+    // denom = sqrt(v)/sqrt(bc2) + eps; p.addcdiv_(m, denom, -lr/bc1) — the
+    // shared expression of every Adam kernel (common.h)
+    adam1(p.x, m.x, v.x, o.x, a.adam);
+    adam1(p.y, m.y, v.y, o.y, a.adam);
+    adam1(p.z, m.z, v.z, o.z, a.adam);
+    adam1(p.w, m.w, v.w, o.w, a.adam);
     st4(a.param + off, p);
     st4(a.m + off, m);
     st4(a.v + off, v);
@@ -294,8 +228,8 @@ constexpr int kWavesPerBlock = 4;
 
 // Row phase: wave w takes the G rows w*G .. w*G+G-1 (of the row list if
 // given).  If all of them have degree <= narrow_max each group gathers its
-// own row (gather_narrow); otherwise the wave walks them one by one with the
-// whole wave per row (gather_rows).  Segment phase: wave row_waves + s
+// own row (gather's NARROW shape); otherwise the wave walks them one by one
+// with the whole wave per row.  Segment phase: wave row_waves + s
 // gathers segment s of a long row into `partial`.
 // With a row list the list length is known only on the device: the grid is
 // capped (kListBlocks) and blocks stride over the list's work items, so a
@@ -328,7 +262,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
     }
     const int64_t deg = have ? end - beg : 0;
     if (G > 1 && __ballot(deg > a.narrow_max) == 0ull) {
-      float4 s = gather_narrow<D, NARROW_UNROLL, MODE, MASKED, WEIGHTED>(a, beg, end, lane);
+      float4 s = gather<D, NARROW_UNROLL, MODE, MASKED, WEIGHTED, true>(a, beg, end, lane);
       if (have) row_epilogue<D>(a, row, s, sub);
       return;
     }
@@ -339,7 +273,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
       const int32_t r = __shfl(row, src);
       const int64_t rb = __shfl((long long)beg, src);
       const int64_t re = __shfl((long long)end, src);
-      float4 s = gather_rows<D, UNROLL, MODE, MASKED, WEIGHTED>(a, rb, re, lane);
+      float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false>(a, rb, re, lane);
       s = combine_groups<D>(s);
       if (lane < LPR) row_epilogue<D>(a, r, s, sub);
     }
@@ -350,7 +284,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
     if (ROWMASK && !bit_set(a.row_mask, row)) return;
     const int64_t beg = a.seg_beg[sg];
     const int64_t end = min(beg + (int64_t)a.split, a.rowptr[row + 1]);
-    float4 s = gather_rows<D, UNROLL, MODE, MASKED, WEIGHTED>(a, beg, end, lane);
+    float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false>(a, beg, end, lane);
     s = combine_groups<D>(s);
     if (lane < LPR) st4(a.partial + sg * D + sub * 4, s);
   }
@@ -371,7 +305,7 @@ __device__ __forceinline__ void block_row(const PropK &a, int32_t row) {
   if (a.split > 0 && end - beg > a.split) return;  // segments handle it (uniform)
   const int64_t q = (end - beg + kWavesPerBlock - 1) / kWavesPerBlock;
   const int64_t wb = min(beg + wid * q, end), we = min(wb + q, end);
-  float4 s = gather_rows<D, UNROLL, MODE, MASKED, WEIGHTED>(a, wb, we, lane);
+  float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false>(a, wb, we, lane);
   s = combine_groups<D>(s);
   if (wid > 0 && lane < LPR) red[wid - 1][sub] = s;
   __syncthreads();
@@ -390,7 +324,7 @@ __device__ __forceinline__ void wave_row(const PropK &a, int32_t row) {
   const int lane = threadIdx.x & 63;
   const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
   if (a.split > 0 && end - beg > a.split) return;  // segments handle it
-  float4 s = gather_rows<D, UNROLL, MODE, MASKED, WEIGHTED>(a, beg, end, lane);
+  float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false>(a, beg, end, lane);
   s = combine_groups<D>(s);
   if (lane < LPR) row_epilogue<D>(a, row, s, lane % LPR);
 }
@@ -412,42 +346,37 @@ MIREC_NO_PK_F32 void prop_kernel(PropK a) {
   constexpr int G = 64 / (D / 4);
   // wave index made provably uniform (SGPR): loop control stays scalar
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if constexpr (!ROWMASK) {
+  if (!ROWMASK || a.row_list == nullptr) {
     prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED>(
         a, (int64_t)blockIdx.x * kWavesPerBlock + wid, a.n_rows, a.row_waves);
-  } else {
-    if (a.row_list == nullptr) {
-      prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED>(
-          a, (int64_t)blockIdx.x * kWavesPerBlock + wid, a.n_rows, a.row_waves);
-      return;
-    }
-    // List mode: the list lengths are known only on the device, so the grid
-    // is capped (kListBlocks) and blocks stride over the work: first one
-    // block per wide row, then G rows per wave of the narrow list, then the
-    // long-row segments.
-    // SPARSE launches mostly scan indices (few seeded neighbours): a wave
-    // per wide row is enough there; gathering launches use a workgroup.
-    constexpr int WPB = (MODE == MIREC_IN_SPARSE) ? kWavesPerBlock : 1;  // wide rows / block
-    const int64_t n_wide = a.wide_list != nullptr ? (int64_t)*a.wide_count : 0;
-    const int64_t wide_blocks = (n_wide + WPB - 1) / WPB;
-    const int64_t nrows = *a.row_count;
-    const int64_t row_waves = (nrows + G - 1) / G;
-    const int64_t waves = row_waves + a.n_seg;
-    const int64_t total = wide_blocks + (waves + kWavesPerBlock - 1) / kWavesPerBlock;
+    return;
+  }
+  // List mode: the list lengths are known only on the device, so the grid
+  // is capped (kListBlocks) and blocks stride over the work: first one
+  // block per wide row, then G rows per wave of the narrow list, then the
+  // long-row segments.
+  // SPARSE launches mostly scan indices (few seeded neighbours): a wave
+  // per wide row is enough there; gathering launches use a workgroup.
+  constexpr int WPB = (MODE == MIREC_IN_SPARSE) ? kWavesPerBlock : 1;  // wide rows / block
+  const int64_t n_wide = a.wide_list != nullptr ? (int64_t)*a.wide_count : 0;
+  const int64_t wide_blocks = (n_wide + WPB - 1) / WPB;
+  const int64_t nrows = *a.row_count;
+  const int64_t row_waves = (nrows + G - 1) / G;
+  const int64_t waves = row_waves + a.n_seg;
+  const int64_t total = wide_blocks + (waves + kWavesPerBlock - 1) / kWavesPerBlock;
 #pragma unroll 1
-    for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
-      if (b < wide_blocks) {
-        if constexpr (WPB == 1) {
-          block_row<D, UNROLL, MODE, MASKED, WEIGHTED>(a, a.wide_list[b]);
-        } else {
-          const int64_t i = b * WPB + wid;
-          if (i < n_wide) wave_row<D, UNROLL, MODE, MASKED, WEIGHTED>(a, a.wide_list[i]);
-        }
+  for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
+    if (b < wide_blocks) {
+      if constexpr (WPB == 1) {
+        block_row<D, UNROLL, MODE, MASKED, WEIGHTED>(a, a.wide_list[b]);
       } else {
-        const int64_t w = (b - wide_blocks) * kWavesPerBlock + wid;
-        if (w < waves)
-          prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED>(a, w, nrows, row_waves);
+        const int64_t i = b * WPB + wid;
+        if (i < n_wide) wave_row<D, UNROLL, MODE, MASKED, WEIGHTED>(a, a.wide_list[i]);
       }
+    } else {
+      const int64_t w = (b - wide_blocks) * kWavesPerBlock + wid;
+      if (w < waves)
+        prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED>(a, w, nrows, row_waves);
     }
   }
 }
@@ -641,22 +570,35 @@ MIREC_NO_PK_F32 void prop_sweep_kernel(PropK a, SweepK s) {
   sweep_work<D, U>(a, s);
 }
 
-template <int D, int UNROLL, int MODE, bool MASKED>
-static void launch_main(dim3 grid, hipStream_t st, const PropK &k) {
-  if constexpr (MODE != MIREC_IN_NONE) {
-    if (k.val != nullptr) {
-      constexpr int MW = MODE | kWeighted;
-      if (k.row_mask != nullptr)
-        hipLaunchKernelGGL((prop_kernel<D, UNROLL, MW, MASKED, true>), grid, dim3(256), 0, st, k);
-      else
-        hipLaunchKernelGGL((prop_kernel<D, UNROLL, MW, MASKED, false>), grid, dim3(256), 0, st, k);
-      return;
-    }
+using PropFn = void (*)(PropK);
+
+// The prop_kernel instantiation of a launch.  SPARSE exists only MASKED (it
+// always filters: by slot >= 0 without an in_mask), NONE only unmasked and
+// unweighted (it reads no neighbours).  The cases stand in the order the
+// kernels have in the code object, which follows their first use here.
+template <int D, int UNROLL>
+static PropFn prop_kernel_for(int mode, bool masked, bool rowmask, bool weighted) {
+  if (mode == MIREC_IN_SPARSE) masked = true;
+  if (mode == MIREC_IN_NONE) weighted = false;
+#define MIREC_PROP_CASE(MODE_W, MASKED)                               \
+  case (MODE_W) * 2 + (MASKED):                                       \
+    return rowmask ? prop_kernel<D, UNROLL, (MODE_W), MASKED, true>   \
+                   : prop_kernel<D, UNROLL, (MODE_W), MASKED, false>;
+  switch ((mode | (weighted ? kWeighted : 0)) * 2 + masked) {
+    MIREC_PROP_CASE(MIREC_IN_PRESCALED | kWeighted, false)
+    MIREC_PROP_CASE(MIREC_IN_PRESCALED, false)
+    MIREC_PROP_CASE(MIREC_IN_PRESCALED | kWeighted, true)
+    MIREC_PROP_CASE(MIREC_IN_PRESCALED, true)
+    MIREC_PROP_CASE(MIREC_IN_RAW | kWeighted, false)
+    MIREC_PROP_CASE(MIREC_IN_RAW, false)
+    MIREC_PROP_CASE(MIREC_IN_RAW | kWeighted, true)
+    MIREC_PROP_CASE(MIREC_IN_RAW, true)
+    MIREC_PROP_CASE(MIREC_IN_SPARSE | kWeighted, true)
+    MIREC_PROP_CASE(MIREC_IN_SPARSE, true)
+    default:  // in_mask is refused with NONE (mirec_propagate_sweep)
+    MIREC_PROP_CASE(MIREC_IN_NONE, false)
   }
-  if (k.row_mask != nullptr)
-    hipLaunchKernelGGL((prop_kernel<D, UNROLL, MODE, MASKED, true>), grid, dim3(256), 0, st, k);
-  else
-    hipLaunchKernelGGL((prop_kernel<D, UNROLL, MODE, MASKED, false>), grid, dim3(256), 0, st, k);
+#undef MIREC_PROP_CASE
 }
 
 template <int D, int UNROLL>
@@ -671,21 +613,10 @@ static int launch_prop(const mirec_csr_t *c, PropK k, int64_t list_cap, int mode
     if (k.wide_list != nullptr) blocks += list_cap;
     blocks = std::min(blocks, kListBlocks);
   }
-  const bool masked = k.in_mask != nullptr;
   if (blocks > 0) {
-    const dim3 g((unsigned)blocks);
-    if (mode == MIREC_IN_PRESCALED && !masked)
-      launch_main<D, UNROLL, MIREC_IN_PRESCALED, false>(g, st, k);
-    else if (mode == MIREC_IN_PRESCALED)
-      launch_main<D, UNROLL, MIREC_IN_PRESCALED, true>(g, st, k);
-    else if (mode == MIREC_IN_RAW && !masked)
-      launch_main<D, UNROLL, MIREC_IN_RAW, false>(g, st, k);
-    else if (mode == MIREC_IN_RAW)
-      launch_main<D, UNROLL, MIREC_IN_RAW, true>(g, st, k);
-    else if (mode == MIREC_IN_SPARSE)  // always filtered (by slot >= 0)
-      launch_main<D, UNROLL, MIREC_IN_SPARSE, true>(g, st, k);
-    else
-      launch_main<D, UNROLL, MIREC_IN_NONE, false>(g, st, k);
+    const PropFn kernel = prop_kernel_for<D, UNROLL>(mode, k.in_mask != nullptr,
+                                                     k.row_mask != nullptr, k.val != nullptr);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, k);
     MIREC_LAUNCH_CHECK();
   }
   if (c->n_long > 0) {
@@ -714,7 +645,7 @@ __global__ __launch_bounds__(256) void prescale_kernel(const float *__restrict__
 // chunk's first and last entries are found by binary search in rowptr (the
 // last row r with rowptr[r] <= e: empty rows are stepped over); a lane then
 // finds the row of its own entry inside that range, which is a single row
-// for a chunk inside a hub.  Like gather_rows, 64 columns are read per
+// for a chunk inside a hub.  Like the wave-per-row gather, 64 columns are read per
 // coalesced load and broadcast; an LPR-lane group takes one entry at a time
 // (one float4 of each row per lane), reduces the products inside the group
 // and hands the sum to the lane that holds the entry, so the 64 results are
@@ -791,10 +722,6 @@ static int launch_edge_dot(const mirec_csr_t *c, const float *a, const float *b,
   MIREC_LAUNCH_CHECK();
   return MIREC_OK;
 }
-
-}  // namespace mirec
-
-namespace mirec {
 
 // The sweep path's qualifying rule; the graph-side part
 // (bipartite, enough rows, a source block larger than L2) is decided where

@@ -23,9 +23,9 @@ TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 OPSEL_HI = re.compile(r"v_pk_\w+_f32\b.*\bop_sel:\[[01,]*1")
 
 
-def kernels(so: str) -> dict:
-    """{kernel symbol: {"mfma": count, "opsel_hi": [instructions]}}"""
-    out = {}
+def code_objects(so: str):
+    """Yields the path of each gfx950 code object in `so` (one per translation
+    unit); the files live until the generator is closed."""
     with tempfile.TemporaryDirectory() as td:
         fb = os.path.join(td, "fatbin")
         subprocess.run([f"{LLVM}/llvm-objcopy", "--dump-section", f".hip_fatbin={fb}", so,
@@ -39,19 +39,32 @@ def kernels(so: str) -> dict:
             subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o",
                             f"--input={bundle}", f"--targets={TARGET}", f"--output={co}"],
                            check=True, capture_output=True)
-            txt = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co],
-                                 capture_output=True, text=True, check=True).stdout
-            fn = None
-            for line in txt.splitlines():
-                m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-                if m:
-                    fn = m.group(1)
-                    out.setdefault(fn, {"mfma": 0, "opsel_hi": []})
-                elif fn is not None:
-                    if "v_mfma" in line:
-                        out[fn]["mfma"] += 1
-                    if OPSEL_HI.search(line):
-                        out[fn]["opsel_hi"].append(line.strip())
+            yield co
+
+
+def disassembly(co: str) -> dict:
+    """{function symbol: its lines of llvm-objdump -d} of one code object."""
+    txt = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co],
+                         capture_output=True, text=True, check=True).stdout
+    out, fn = {}, None
+    for line in txt.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+        if m:
+            fn = m.group(1)
+            out.setdefault(fn, [])
+        elif fn is not None:
+            out[fn].append(line)
+    return out
+
+
+def kernels(so: str) -> dict:
+    """{kernel symbol: {"mfma": count, "opsel_hi": [instructions]}}"""
+    out = {}
+    for co in code_objects(so):
+        for fn, lines in disassembly(co).items():
+            v = out.setdefault(fn, {"mfma": 0, "opsel_hi": []})
+            v["mfma"] += sum("v_mfma" in line for line in lines)
+            v["opsel_hi"] += [line.strip() for line in lines if OPSEL_HI.search(line)]
     return out
 
 
