@@ -20,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MIREC_LIB") or os.path.join(_HERE, "libmirec.so")
 
 MIREC_OK = 0
+ERR_WORKSPACE = 4  # MIREC_ERR_WORKSPACE
 IN_PRESCALED, IN_RAW, IN_SPARSE, IN_NONE = 0, 1, 2, 3
 SUPPORTED_DIMS = (4, 8, 16, 32, 64, 128, 256)
 
@@ -75,6 +76,17 @@ class Sweep(Structure):
     ]
 
 
+class SweepWave(Structure):
+    """mirec_sweep_wave_t (per-wave column-sweep layout of a block of rows)."""
+    _fields_ = [
+        ("row0", c_int64), ("n_rows", c_int64), ("src0", c_int64), ("n_src", c_int64),
+        ("n_slots", c_int64),
+        ("tile_rows", c_int32), ("wave_rows", c_int32), ("n_tiles", c_int32),
+        ("band_rows", c_int32), ("grid", c_int32), ("_pad", c_int32),
+        ("wptr", c_void_p), ("slot", c_void_p),
+    ]
+
+
 class RowGradGroup(Structure):
     """mirec_row_grad_group_t (one group of table-gradient row contributions)."""
     _fields_ = [
@@ -117,6 +129,11 @@ SIGNATURES = {
     "mirec_sweep_build": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32,
                                   c_int32, c_void_p, c_void_p]),
     "mirec_sweep_groups": (c_int, [c_int32]),
+    "mirec_sweep_wave_sizeof": (c_size_t, []),
+    "mirec_sweep_wave_build": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                       c_int32, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
+    "mirec_propagate_sweep_wave": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(SweepWave),
+                                           POINTER(SweepWave), c_void_p]),
     "mirec_edge_dot": (c_int, [POINTER(CSR), c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "mirec_prescale": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "mirec_shard_pack": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_int64,
@@ -371,6 +388,8 @@ def _load():
         raise ImportError("struct layout mismatch: mirec_row_grad_group_t")
     if lib.mirec_sweep_sizeof() != ctypes.sizeof(Sweep):
         raise ImportError("struct layout mismatch: mirec_sweep_t")
+    if lib.mirec_sweep_wave_sizeof() != ctypes.sizeof(SweepWave):
+        raise ImportError("struct layout mismatch: mirec_sweep_wave_t")
     return lib
 
 

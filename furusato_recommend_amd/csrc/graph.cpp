@@ -259,6 +259,129 @@ extern "C" int mirec_sweep_build(const int64_t *rowptr, const int32_t *col, int6
   return MIREC_OK;
 }
 
+extern "C" size_t mirec_sweep_wave_sizeof(void) { return sizeof(mirec_sweep_wave_t); }
+
+// Per-wave form of the column-sweep layout (mirec_sweep_wave_t).  A wave's
+// rows are merged into one stream in (column, CSR position) order and cut
+// into steps of 4 slots that name 4 different rows, so the 4 lane groups of
+// the wave add into their LDS rows in the same instruction without a race.
+// A step takes, among the pending entries less than MIREC_SWEEP_LOOKAHEAD
+// merged positions past the oldest pending one, the earliest whose row it
+// does not hold yet; an entry skipped for its row keeps every later entry of
+// that row out of the step too, so a row's terms keep their merged order.
+// What a step cannot fill is padding (local row -1, the column of the slot
+// before it); the stream is padded to whole batches the same way.  The padded
+// length depends on the data: the streams are scheduled into per-thread
+// buffers first, then placed.  Tiles are split over up to 16 threads.
+extern "C" int mirec_sweep_wave_build(const int64_t *rowptr, const int32_t *col, int64_t row0,
+                                      int64_t n_rows, int64_t src0, int64_t n_src,
+                                      int32_t tile_rows, int64_t *wptr, int64_t *slot,
+                                      int64_t slot_cap, int64_t *n_slots) {
+  constexpr int W = MIREC_SWEEP_WAVES, LOOK = MIREC_SWEEP_LOOKAHEAD, BATCH = MIREC_SWEEP_BATCH;
+  if (rowptr == nullptr || wptr == nullptr || n_slots == nullptr || row0 < 0 || src0 < 0 ||
+      n_src < 0 || n_rows < 0 || tile_rows <= 0 || slot_cap < 0 ||
+      (slot == nullptr && slot_cap > 0))
+    return MIREC_ERR_ARG;
+  const int64_t n_tiles = (n_rows + tile_rows - 1) / tile_rows;
+  if (n_tiles >= INT32_MAX / W) return MIREC_ERR_RANGE;
+  const int64_t wave_rows = (tile_rows + W - 1) / W;
+  const int64_t total = rowptr[row0 + n_rows] - rowptr[row0];
+  if (total < 0 || (total > 0 && col == nullptr)) return MIREC_ERR_ARG;
+  const int n_thr = (int)std::max<int64_t>(
+      1, std::min<int64_t>(16, std::min<int64_t>((int64_t)std::thread::hardware_concurrency(),
+                                                 total / (1 << 16) + 1)));
+  std::vector<int> bad(n_thr, 0);
+  std::vector<std::vector<int64_t>> buf(n_thr);  // thread th's streams, in its tile order
+  auto work = [&](int th) {
+    std::vector<uint64_t> key;
+    std::vector<int32_t> lrow, mrow, mcol;
+    std::vector<char> taken;
+    std::vector<int64_t> &o = buf[th];
+    for (int64_t t = th; t < n_tiles; t += n_thr) {
+      const int64_t tile_end = std::min<int64_t>((t + 1) * tile_rows, n_rows);
+      for (int64_t w = 0; w < W; ++w) {
+        const int64_t r0 = std::min<int64_t>(t * tile_rows + w * wave_rows, tile_end);
+        const int64_t r1 = std::min<int64_t>(r0 + wave_rows, tile_end);
+        const int64_t e0 = rowptr[row0 + r0], e1 = rowptr[row0 + r1];
+        if (e1 - e0 >= INT32_MAX) {
+          bad[th] = 1;
+          return;
+        }
+        const int64_t n = e1 - e0;
+        key.resize(n);
+        lrow.resize(n);
+        for (int64_t r = r0; r < r1; ++r)
+          for (int64_t e = rowptr[row0 + r]; e < rowptr[row0 + r + 1]; ++e) {
+            const int32_t c = col[e];
+            if (c < src0 || c >= src0 + n_src) {
+              bad[th] = 1;
+              return;
+            }
+            key[e - e0] = ((uint64_t)(uint32_t)c << 32) | (uint64_t)(e - e0);
+            lrow[e - e0] = (int32_t)(r - t * tile_rows);
+          }
+        std::sort(key.begin(), key.end());
+        mrow.resize(n);
+        mcol.resize(n);
+        for (int64_t k = 0; k < n; ++k) {
+          mcol[k] = (int32_t)(key[k] >> 32);
+          mrow[k] = lrow[(uint32_t)key[k]];
+        }
+        taken.assign(n, 0);
+        const size_t begin = o.size();
+        int64_t head = 0;
+        int32_t last_col = 0;
+        while (head < n) {
+          int32_t rows[4];
+          int cnt = 0;
+          const int64_t lim = std::min<int64_t>(n, head + LOOK);
+          for (int64_t i = head; i < lim && cnt < 4; ++i) {
+            if (taken[i]) continue;
+            bool clash = false;
+            for (int q = 0; q < cnt; ++q) clash |= rows[q] == mrow[i];
+            if (clash) continue;
+            taken[i] = 1;
+            rows[cnt++] = mrow[i];
+            last_col = mcol[i];
+            o.push_back((int64_t)(((uint64_t)(uint32_t)mrow[i] << 32) | (uint32_t)mcol[i]));
+          }
+          const int64_t pad = (int64_t)(0xffffffffull << 32 | (uint32_t)last_col);
+          for (; cnt < 4; ++cnt) o.push_back(pad);
+          while (head < n && taken[head]) ++head;
+        }
+        const int64_t pad = (int64_t)(0xffffffffull << 32 | (uint32_t)last_col);
+        while ((o.size() - begin) % BATCH != 0) o.push_back(pad);
+        wptr[t * W + w + 1] = (int64_t)(o.size() - begin);  // length; summed below
+      }
+    }
+  };
+  {
+    std::vector<std::thread> th;
+    for (int t = 1; t < n_thr; ++t) th.emplace_back(work, t);
+    work(0);
+    for (auto &x : th) x.join();
+  }
+  for (int b : bad)
+    if (b) return MIREC_ERR_RANGE;
+  wptr[0] = 0;
+  for (int64_t s = 0; s < n_tiles * W; ++s) wptr[s + 1] += wptr[s];
+  *n_slots = wptr[n_tiles * W];
+  if (*n_slots > slot_cap) return MIREC_ERR_WORKSPACE;
+  auto place = [&](int th) {
+    const int64_t *src = buf[th].data();
+    for (int64_t t = th; t < n_tiles; t += n_thr) {
+      const int64_t len = wptr[(t + 1) * W] - wptr[t * W];
+      std::copy(src, src + len, slot + wptr[t * W]);
+      src += len;
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < n_thr; ++t) th.emplace_back(place, t);
+  place(0);
+  for (auto &x : th) x.join();
+  return MIREC_OK;
+}
+
 // Per-user positive CDF for the weighted samplers (the sample_pow option,
 // negative_sample.py:53-56): probs[e - rowptr[0]] = the probability of entry
 // e of its user row (rows 0 .. n_users - 1, the allPos order), each row's

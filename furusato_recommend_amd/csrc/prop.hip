@@ -570,6 +570,142 @@ MIREC_NO_PK_F32 void prop_sweep_kernel(PropK a, SweepK s) {
   sweep_work<D, U>(a, s);
 }
 
+// ---- per-wave form of the sweep (mirec_sweep_wave_t).  The four lane groups
+// of a wave above walk four private streams in lockstep per ENTRY, so their
+// column positions drift apart; here a wave walks ONE stream, its rows'
+// entries merged by column and cut on the host into steps of 4 slots that
+// name 4 different rows (or padding): one cursor per wave, and the 4 groups
+// add into different LDS rows in the same instruction.  Slot k*16 + u*4 + g
+// of a 64-slot chunk (one coalesced 512-B load, the next chunk prefetched)
+// goes to lane group g as step u of batch k.  A pad slot carries a column
+// of the stream (its load hits a line just used) and local row -1 (dropped),
+// so every row load is unconditional and unclamped.  Same mechanics
+// otherwise: two register buffers, the previous batch added while the next
+// is in flight, a row's terms added one at a time in stream order (for the
+// item rows bitwise what prop_sweep_kernel gives), bare s_barrier per band,
+// decided from the first slot of a batch: the oldest pending entry, no
+// later slot has a smaller column.  Every wave executes exactly n_bands - 1
+// of them per tile.
+// Passes: workgroup b takes the tiles b, b + grid, ...; nothing waits across
+// workgroups and nothing depends on which of them are resident.
+struct SweepWaveK {
+  const int64_t *wptr;
+  const long long *slot;  // (lrow << 32) | col per slot; lrow -1 = padding
+  int64_t n_slots;
+  int64_t row0;
+  int64_t n_rows;
+  int64_t src0;
+  int32_t tile_rows;
+  int32_t wave_rows;
+  int32_t n_tiles;
+  int32_t band_rows;
+  int32_t n_bands;
+};
+
+template <int D, int U>
+__device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK &s) {
+  constexpr int LPR = D / 4;
+  constexpr int G = 64 / LPR;          // lane groups = slots per step
+  constexpr int NB = 64 / (U * G);     // batches per 64-slot chunk
+  static_assert(G == 4 && U * G == MIREC_SWEEP_BATCH && kSweepThreads / 64 == MIREC_SWEEP_WAVES,
+                "the host layout's steps, batches and waves");
+  extern __shared__ float4 sweep_acc[];  // [tile_rows][LPR]
+  const int lane = threadIdx.x & 63;
+  const int sub = lane % LPR;
+  const int g = lane / LPR;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long kPadRow = (long long)0xffffffff00000000ull;
+  const int64_t last = s.n_slots - 1;  // >= 0 (checked by the host)
+#pragma unroll 1
+  for (int tile = blockIdx.x; tile < s.n_tiles; tile += gridDim.x) {
+    const int64_t tile_row0 = (int64_t)tile * s.tile_rows;
+    const int tile_len = (int)min((int64_t)s.tile_rows, s.n_rows - tile_row0);
+    const int lr0 = min(wid * s.wave_rows, tile_len);
+    const int lr1 = min(lr0 + s.wave_rows, tile_len);
+    for (int lr = lr0 + g; lr < lr1; lr += G) sweep_acc[lr * LPR + sub] = f4_zero();
+    int64_t pos = s.wptr[(int64_t)tile * MIREC_SWEEP_WAVES + wid];
+    const int64_t end = s.wptr[(int64_t)tile * MIREC_SWEEP_WAVES + wid + 1];
+    const int n_batches = __builtin_amdgcn_readfirstlane((int)((end - pos) / (U * G)));
+    // slots past the stream's end are padding (their column: a slot of the
+    // layout, inside the source block)
+    long long cur = __builtin_nontemporal_load(s.slot + min(pos + lane, last));
+    if (lane >= n_batches * (U * G)) cur |= kPadRow;
+    int band = 0;
+    int64_t hi = s.src0 + s.band_rows;
+    float4 pv[U];
+    int pr[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      pv[u] = f4_zero();
+      pr[u] = -1;
+    }
+#pragma unroll 1
+    for (int b0 = 0; b0 < n_batches; b0 += NB) {
+      long long nxt = __builtin_nontemporal_load(s.slot + min(pos + 64 + lane, last));
+      if (b0 * (U * G) + 64 + lane >= n_batches * (U * G)) nxt |= kPadRow;
+      const int ccol = (int)(cur & 0xffffffffll);
+      const int crow = (int)(cur >> 32);
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+        // the wave enters the next band once its oldest pending entry lies
+        // beyond the current one (batches past the end decide nothing)
+        const int nc = __builtin_amdgcn_readlane(ccol, k * U * G);
+        while (b0 + k < n_batches && band + 1 < s.n_bands && (int64_t)nc >= hi) {
+          __builtin_amdgcn_s_barrier();
+          ++band;
+          hi += s.band_rows;
+        }
+        float4 v[U];
+        int r[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int src = k * U * G + u * G + g;
+          const int j = __shfl(ccol, src);
+          r[u] = __shfl(crow, src);
+          v[u] = ld4(a.x_in + (int64_t)j * D + sub * 4);
+        }
+        // add the PREVIOUS batch while this one is in flight; the G slots of
+        // a step name different rows, so the groups do not race
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (pr[u] >= 0) {
+            float4 *p = &sweep_acc[pr[u] * LPR + sub];
+            *p = f4_add(*p, pv[u]);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          pv[u] = v[u];
+          pr[u] = r[u];
+        }
+      }
+      pos += 64;
+      cur = nxt;
+    }
+    while (band + 1 < s.n_bands) {  // every wave executes the same number of barriers
+      __builtin_amdgcn_s_barrier();
+      ++band;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (pr[u] >= 0) {
+        float4 *p = &sweep_acc[pr[u] * LPR + sub];
+        *p = f4_add(*p, pv[u]);
+      }
+    }
+    // rows are private to their wave
+    for (int lr = lr0 + g; lr < lr1; lr += G)
+      row_epilogue<D>(a, s.row0 + tile_row0 + lr, sweep_acc[lr * LPR + sub], sub);
+    __syncthreads();  // the accumulators are reused by the workgroup's next tile
+  }
+}
+
+template <int D, int U>
+__global__ __launch_bounds__(kSweepThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+MIREC_NO_PK_F32 void prop_sweep_wave_kernel(PropK a, SweepWaveK s) {
+  sweep_wave_work<D, U>(a, s);
+}
+
 using PropFn = void (*)(PropK);
 
 // The prop_kernel instantiation of a launch.  SPARSE exists only MASKED (it
@@ -725,13 +861,17 @@ static int launch_edge_dot(const mirec_csr_t *c, const float *a, const float *b,
 
 // The sweep path's qualifying rule; the graph-side part
 // (bipartite, enough rows, a source block larger than L2) is decided where
-// the layout is built.
-static bool sweep_qualifies(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sweep_t *sw) {
-  if (sw == nullptr || p->dim != 64) return false;
-  if (c->val != nullptr) return false;  // the sweep layout carries no values
+// the layout is built.  First the launch-side part, shared by both forms.
+static bool sweep_launch_qualifies(const mirec_csr_t *c, const mirec_prop_t *p) {
+  if (p->dim != 64) return false;
+  if (c->val != nullptr) return false;  // the sweep layouts carry no values
   if (p->in_mode != MIREC_IN_PRESCALED) return false;
   if (p->in_mask != nullptr || p->row_mask != nullptr || p->row_list != nullptr) return false;
-  if (c->n_seg > 0) return false;
+  return c->n_seg == 0;
+}
+
+static bool sweep_qualifies(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sweep_t *sw) {
+  if (sw == nullptr || !sweep_launch_qualifies(c, p)) return false;
   if (sw->gptr == nullptr || sw->ent == nullptr || sw->n_rows <= 0 || sw->n_tiles <= 0)
     return false;
   if (sw->row0 < 0 || sw->row0 + sw->n_rows != c->n_rows || sw->n_src > c->n_rows) return false;
@@ -741,6 +881,16 @@ static bool sweep_qualifies(const mirec_csr_t *c, const mirec_prop_t *p, const m
   if ((int64_t)sw->n_tiles * sw->tile_rows < sw->n_rows) return false;
   if ((int64_t)sw->tile_rows * 64 * 4 > kSweepLdsMax) return false;
   return true;
+}
+
+// Rows [0, row0) of a launch whose other rows were swept: the row kernel.
+template <int D, int UNROLL>
+static int launch_head(const mirec_csr_t *c, const PropK &k, int64_t row0, hipStream_t st) {
+  mirec_csr_t head = *c;
+  head.n_rows = row0;
+  PropK kh = k;
+  kh.n_rows = row0;  // the last wave's groups past row0 - 1 stay idle
+  return launch_prop<D, UNROLL>(&head, kh, 0, MIREC_IN_PRESCALED, st);
 }
 
 // Item rows by the sweep kernel, rows [0, row0) by the row kernel.
@@ -762,11 +912,42 @@ static int launch_sweep(const mirec_csr_t *c, const PropK &k, const mirec_sweep_
                      lds, st, k, s);
   MIREC_LAUNCH_CHECK();
   if (sw->row0 == 0) return MIREC_OK;
-  mirec_csr_t head = *c;
-  head.n_rows = sw->row0;
-  PropK kh = k;
-  kh.n_rows = sw->row0;  // the last wave's groups past row0 - 1 stay idle
-  return launch_prop<D, UNROLL>(&head, kh, 0, MIREC_IN_PRESCALED, st);
+  return launch_head<D, UNROLL>(c, k, sw->row0, st);
+}
+
+// A well-formed per-wave layout of the rows [row0, row0 + n_rows) of `c`.
+static bool sweep_wave_valid(const mirec_csr_t *c, const mirec_sweep_wave_t *w, int64_t row0,
+                             int64_t n_rows) {
+  if (w == nullptr || w->wptr == nullptr || w->slot == nullptr || w->n_slots <= 0) return false;
+  if (w->row0 != row0 || w->n_rows != n_rows || n_rows <= 0 || w->n_tiles <= 0) return false;
+  if (w->src0 < 0 || w->n_src <= 0 || w->src0 + w->n_src > c->n_rows) return false;
+  if (w->tile_rows <= 0 || w->wave_rows <= 0 || w->band_rows <= 0) return false;
+  if ((int64_t)w->wave_rows * MIREC_SWEEP_WAVES < w->tile_rows) return false;
+  if ((int64_t)w->n_tiles * w->tile_rows < n_rows) return false;
+  if ((int64_t)(w->n_tiles - 1) * w->tile_rows >= n_rows) return false;
+  if ((int64_t)w->tile_rows * 64 * 4 > kSweepLdsMax) return false;
+  return w->grid > 0 && w->grid <= w->n_tiles;
+}
+
+template <int D>
+static int launch_sweep_wave(const PropK &k, const mirec_sweep_wave_t *w, hipStream_t st) {
+  SweepWaveK s;
+  s.wptr = w->wptr;
+  s.slot = reinterpret_cast<const long long *>(w->slot);
+  s.n_slots = w->n_slots;
+  s.row0 = w->row0;
+  s.n_rows = w->n_rows;
+  s.src0 = w->src0;
+  s.tile_rows = w->tile_rows;
+  s.wave_rows = w->wave_rows;
+  s.n_tiles = w->n_tiles;
+  s.band_rows = w->band_rows;
+  s.n_bands = (int32_t)std::max<int64_t>(1, (w->n_src + w->band_rows - 1) / w->band_rows);
+  const size_t lds = (size_t)w->tile_rows * D * sizeof(float);
+  hipLaunchKernelGGL((prop_sweep_wave_kernel<D, 4>), dim3((unsigned)w->grid),
+                     dim3(kSweepThreads), lds, st, k, s);
+  MIREC_LAUNCH_CHECK();
+  return MIREC_OK;
 }
 
 }  // namespace mirec
@@ -775,14 +956,13 @@ extern "C" int mirec_sweep_groups(int32_t dim) {
   return dim == 64 ? mirec::kSweepThreads / (64 / 4) : 0;
 }
 
-extern "C" int mirec_propagate(const mirec_csr_t *c, const mirec_prop_t *p,
-                               mirec_stream_t stream) {
-  return mirec_propagate_sweep(c, p, nullptr, stream);
-}
+namespace mirec {
 
-extern "C" int mirec_propagate_sweep(const mirec_csr_t *c, const mirec_prop_t *p,
-                                     const mirec_sweep_t *sw, mirec_stream_t stream) {
-  using namespace mirec;
+// The one body of the three propagate entries: at most one of `sw` (group
+// form) and `wi` (wave form, `wu` optional beside it) is given.
+static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sweep_t *sw,
+                     const mirec_sweep_wave_t *wi, const mirec_sweep_wave_t *wu,
+                     mirec_stream_t stream) {
   MIREC_CHECK_ARG(c != nullptr && p != nullptr);
   MIREC_CHECK_ARG(c->rowptr != nullptr && c->dinv != nullptr && c->n_rows >= 0);
   MIREC_CHECK_ARG(c->nnz == 0 || c->col != nullptr);
@@ -839,6 +1019,13 @@ extern "C" int mirec_propagate_sweep(const mirec_csr_t *c, const mirec_prop_t *p
   const int64_t cap = p->row_list_cap;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (sweep_qualifies(c, p, sw)) return launch_sweep<64, 4>(c, k, sw, st);
+  if (wi != nullptr && sweep_launch_qualifies(c, p) &&
+      sweep_wave_valid(c, wi, wi->row0, c->n_rows - wi->row0)) {
+    const int rc = launch_sweep_wave<64>(k, wi, st);
+    if (rc != MIREC_OK || wi->row0 == 0) return rc;
+    if (sweep_wave_valid(c, wu, 0, wi->row0)) return launch_sweep_wave<64>(k, wu, st);
+    return launch_head<64, 4>(c, k, wi->row0, st);
+  }
   switch (p->dim) {
     case 4: return launch_prop<4, 1>(c, k, cap, p->in_mode, st);
     case 8: return launch_prop<8, 1>(c, k, cap, p->in_mode, st);
@@ -849,6 +1036,25 @@ extern "C" int mirec_propagate_sweep(const mirec_csr_t *c, const mirec_prop_t *p
     case 256: return launch_prop<256, 8>(c, k, cap, p->in_mode, st);
   }
   return MIREC_ERR_DIM;
+}
+
+}  // namespace mirec
+
+extern "C" int mirec_propagate(const mirec_csr_t *c, const mirec_prop_t *p,
+                               mirec_stream_t stream) {
+  return mirec_propagate_sweep(c, p, nullptr, stream);
+}
+
+extern "C" int mirec_propagate_sweep(const mirec_csr_t *c, const mirec_prop_t *p,
+                                     const mirec_sweep_t *sw, mirec_stream_t stream) {
+  return mirec::propagate(c, p, sw, nullptr, nullptr, stream);
+}
+
+extern "C" int mirec_propagate_sweep_wave(const mirec_csr_t *c, const mirec_prop_t *p,
+                                          const mirec_sweep_wave_t *items,
+                                          const mirec_sweep_wave_t *users,
+                                          mirec_stream_t stream) {
+  return mirec::propagate(c, p, nullptr, items, users, stream);
 }
 
 extern "C" int mirec_edge_dot(const mirec_csr_t *c, const float *a, const float *b, int32_t dim,

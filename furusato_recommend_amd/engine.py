@@ -43,6 +43,11 @@ from ._lib import (IN_NONE, IN_PRESCALED, IN_RAW, IN_SPARSE, Prop, adam_hparams,
                    check, lib, ptr)
 from .graph import Graph
 
+# Defaults of PropagationEngine.sweep_form / sweep_users, set by the A/B
+# measurements of DESIGN.md §14.
+SWEEP_FORM = "wave"
+SWEEP_USERS = True
+
 
 def prop_launch_bytes(in_mode: int, n_nodes: int, nnz: int, dim: int, *, slot=False,
                       xs_out=False, addend=False, out=False, adam=False, weighted=False) -> int:
@@ -285,7 +290,15 @@ class PropagationEngine:
         # edge-weighted graph never does: every launch below then runs the
         # weighted row kernel, csr.val carried by the graph)
         self.use_sweep = True
-        self.sweep = graph.sweep_layout(self.dim)
+        self._group_sizes = (None, None, None)
+        # the sweep's form: "group" = a stream per lane group
+        # (self.sweep), "wave" = a stream per wave with conflict-free steps
+        # (self.sweep_wave); sweep_users also sweeps the user rows (wave form
+        # only, self.sweep_wave_users) so that a full launch runs no row kernel
+        self._wave_sizes = {"items": (None, None), "users": (None, None), "max_grid": None}
+        self.sweep_wave = self.sweep_wave_users = None
+        self._sweep_form, self._sweep_users = SWEEP_FORM, SWEEP_USERS
+        self._wave_layouts()
         # first backward layer's neighbour filter: "slot" (one dependent load;
         # best for one batch), "bytemap" (S byte map, then the slot of the
         # hits), "dense" (seed rows scattered into a zero [N, D] table and
@@ -370,10 +383,18 @@ class PropagationEngine:
         if ev is not None:
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record()
-        sw = self.sweep if (self.use_sweep and g is self.g) else None
-        check(lib.mirec_propagate_sweep(g.csr_ptr(), ctypes.byref(p),
-                                        sw.ptr() if sw is not None else None,
-                                        _lib.stream_handle()), "propagate")
+        on = self.use_sweep and g is self.g
+        if on and self._sweep_form == "wave":
+            wi, wu = self.sweep_wave, self.sweep_wave_users if self._sweep_users else None
+            check(lib.mirec_propagate_sweep_wave(g.csr_ptr(), ctypes.byref(p),
+                                                 wi.ptr() if wi is not None else None,
+                                                 wu.ptr() if wu is not None else None,
+                                                 _lib.stream_handle()), "propagate")
+        else:
+            sw = self.sweep if on else None
+            check(lib.mirec_propagate_sweep(g.csr_ptr(), ctypes.byref(p),
+                                            sw.ptr() if sw is not None else None,
+                                            _lib.stream_handle()), "propagate")
         if ev is not None:
             e.record()
             kind = (in_mode, in_mask is not None, row_mask is not None, out_mask is not None)
@@ -432,10 +453,59 @@ class PropagationEngine:
         self._masks_ready = True
 
     def set_sweep_sizes(self, tile_rows: int | None = None, group_rows: int | None = None,
-                        band_rows: int | None = None):
-        """Rebuild the sweep layout with explicit sizes (tuning; tests force
-        many tiles and bands on a small graph).  All None = the defaults."""
-        self.sweep = self.g.sweep_layout(self.dim, tile_rows, group_rows, band_rows)
+                        band_rows: int | None = None, *, wave_items=None, wave_users=None,
+                        max_grid: int | None = None):
+        """Rebuild the sweep layouts with explicit sizes (tuning; tests force
+        many tiles and bands on a small graph).  All None = the defaults.
+        The positional sizes are the group form's; ``wave_items`` and
+        ``wave_users`` are (tile_rows, band_rows) of the wave form's two
+        blocks (the item block takes the positional tile_rows and band_rows
+        when not given), ``max_grid`` caps its workgroups (several passes on
+        a small graph)."""
+        self._group_sizes = (tile_rows, group_rows, band_rows)
+        self._wave_sizes = {"items": tuple(wave_items or (tile_rows, band_rows)),
+                            "users": tuple(wave_users or (None, None)), "max_grid": max_grid}
+        self.sweep_wave = self.sweep_wave_users = None
+        self._wave_layouts()
+
+    @property
+    def sweep(self):
+        """The group form's layout of the item rows (None: the graph does not
+        qualify), built when first asked for."""
+        return self.g.sweep_layout(self.dim, *self._group_sizes)
+
+    def _wave_layouts(self):
+        """Build the wave-form layouts the switches ask for (cached per graph
+        and sizes by Graph.sweep_wave_layout)."""
+        if self._sweep_form != "wave":
+            return
+        ws = self._wave_sizes
+        if self.sweep_wave is None:
+            self.sweep_wave = self.g.sweep_wave_layout(self.dim, "items", *ws["items"],
+                                                       max_grid=ws["max_grid"])
+        if self._sweep_users and self.sweep_wave is not None and self.sweep_wave_users is None:
+            self.sweep_wave_users = self.g.sweep_wave_layout(self.dim, "users", *ws["users"],
+                                                             max_grid=ws["max_grid"])
+
+    @property
+    def sweep_form(self) -> str:
+        return self._sweep_form
+
+    @sweep_form.setter
+    def sweep_form(self, form: str):
+        if form not in ("wave", "group"):
+            raise ValueError(f"sweep_form: 'wave' or 'group', got {form!r}")
+        self._sweep_form = form
+        self._wave_layouts()
+
+    @property
+    def sweep_users(self) -> bool:
+        return self._sweep_users
+
+    @sweep_users.setter
+    def sweep_users(self, on: bool):
+        self._sweep_users = bool(on)
+        self._wave_layouts()
 
     def _wide_bits(self) -> torch.Tensor:
         """Bit v of word v // 32: node v's degree > narrow_max (the row lists'

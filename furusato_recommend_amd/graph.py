@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CSR, Sweep, check, lib
+from ._lib import CSR, Sweep, SweepWave, check, lib
 
 # Rows longer than this are split into segments (load balance on skewed
 # item popularity).  2048 neighbours x 256 B = 512 KiB of gather per segment.
@@ -36,6 +36,7 @@ DEFAULT_SPLIT = 2048
 SWEEP_BAND_BYTES = 1 << 20
 SWEEP_LDS_BYTES = 64 << 10
 SWEEP_L2_BYTES = 4 << 20
+SWEEP_WAVES = 8  # MIREC_SWEEP_WAVES: the waves of a sweep workgroup
 
 
 class SweepLayout:
@@ -43,6 +44,17 @@ class SweepLayout:
     gptr: torch.Tensor
     ent: torch.Tensor
     desc: Sweep
+
+    def ptr(self):
+        return ctypes.byref(self.desc)
+
+
+class SweepWaveLayout:
+    """Device arrays of a per-wave column-sweep layout and their descriptor."""
+    wptr: torch.Tensor
+    slot: torch.Tensor
+    desc: SweepWave
+    n_entries: int  # real slots (desc.n_slots counts the padding too)
 
     def ptr(self):
         return ctypes.byref(self.desc)
@@ -342,6 +354,86 @@ class Graph:
                          group_rows=group_rows, groups=groups.value, n_tiles=n_tiles.value,
                          band_rows=band_rows, _pad=0, gptr=lay.gptr.data_ptr(),
                          ent=lay.ent.data_ptr())
+        return lay
+
+    def sweep_wave_layout(self, dim: int, block: str = "items", tile_rows: int | None = None,
+                          band_rows: int | None = None, max_grid: int | None = None):
+        """The per-wave form of the column-sweep layout (mirec_sweep_wave_t,
+        DESIGN.md §14) of the item rows (``block="items"``, gathering from the
+        user block) or of the user rows (``"users"``, gathering from the item
+        block), or None when the graph does not qualify: the conditions of
+        ``sweep_layout``, and for the user rows with default sizes an item
+        block larger than one XCD's L2.  Defaults: for the items two tiles per
+        CU (one pass), for the users tiles of SWEEP_LDS_BYTES swept in passes
+        by two workgroups per CU; bands of SWEEP_BAND_BYTES of source rows.
+        ``max_grid`` caps the workgroups launched (tests force several passes
+        on a small graph).  Built once per (graph, sizes)."""
+        key = ("wave", dim, block, tile_rows, band_rows, max_grid)
+        cache = self.__dict__.setdefault("_sweeps", {})
+        if key in cache:
+            return cache[key]
+        cache[key] = lay = self._build_sweep_wave(dim, block, tile_rows, band_rows, max_grid)
+        return lay
+
+    def _build_sweep_wave(self, dim, block, tile_rows, band_rows, max_grid):
+        nu, mi = self.n_users, self.m_items
+        if block not in ("items", "users"):
+            raise ValueError(f"block: 'items' or 'users', got {block!r}")
+        if self.val is not None:  # the sweep layouts carry no values
+            return None
+        if not (self.symmetric and nu > 0 and mi > 0 and nu + mi == self.n_nodes):
+            return None
+        if self.n_seg > 0 or lib.mirec_sweep_groups(dim) == 0 or self.device.type != "cuda":
+            return None
+        explicit = not (tile_rows is None and band_rows is None)
+        row_bytes = dim * 4
+        max_tile = SWEEP_LDS_BYTES // row_bytes
+        n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
+        if not explicit:
+            if mi < n_cu or nu * row_bytes <= SWEEP_L2_BYTES:
+                return None
+            if block == "users" and mi * row_bytes <= SWEEP_L2_BYTES:
+                return None
+        row0, n_rows, src0, n_src = (nu, mi, 0, nu) if block == "items" else (0, nu, nu, mi)
+        if tile_rows is None:
+            tile_rows = max_tile
+            if block == "items":
+                tile_rows = min(max_tile, max(1, -(-mi // (2 * n_cu))))
+        if band_rows is None:
+            band_rows = max(1, SWEEP_BAND_BYTES // row_bytes)
+        tile_rows, band_rows = int(tile_rows), int(band_rows)
+        if not 0 < tile_rows <= max_tile or band_rows <= 0:
+            raise ValueError(f"sweep sizes out of range: tile_rows {tile_rows} (max {max_tile}), "
+                             f"band_rows {band_rows}")
+        n_tiles = -(-n_rows // tile_rows)
+        n_ent = int(self.rowptr_host[row0 + n_rows] - self.rowptr_host[row0])
+        if n_ent == 0:
+            return None
+        wptr = np.empty(n_tiles * SWEEP_WAVES + 1, np.int64)
+        # room for the usual padding; the builder says what it needs otherwise
+        slot = np.empty(n_ent + n_ent // 8 + 16 * n_tiles * SWEEP_WAVES, np.int64)
+        n_slots = ctypes.c_int64(0)
+        for _ in range(2):
+            rc = lib.mirec_sweep_wave_build(self.rowptr_host.ctypes.data,
+                                            self.col_host.ctypes.data, row0, n_rows, src0, n_src,
+                                            tile_rows, wptr.ctypes.data, slot.ctypes.data,
+                                            slot.shape[0], ctypes.byref(n_slots))
+            if rc != _lib.ERR_WORKSPACE:
+                break
+            slot = np.empty(n_slots.value, np.int64)
+        check(rc, "sweep_wave_build")
+        grid = min(n_tiles, 2 * n_cu)
+        if max_grid is not None:
+            grid = max(1, min(grid, int(max_grid)))
+        lay = SweepWaveLayout()
+        lay.n_entries = n_ent
+        lay.wptr = torch.from_numpy(wptr).to(self.device)
+        lay.slot = torch.from_numpy(slot[:n_slots.value]).to(self.device)
+        lay.desc = SweepWave(row0=row0, n_rows=n_rows, src0=src0, n_src=n_src,
+                             n_slots=n_slots.value, tile_rows=tile_rows,
+                             wave_rows=-(-tile_rows // SWEEP_WAVES), n_tiles=n_tiles,
+                             band_rows=band_rows, grid=grid, _pad=0,
+                             wptr=lay.wptr.data_ptr(), slot=lay.slot.data_ptr())
         return lay
 
     def set_positive_probs(self, probs) -> None:

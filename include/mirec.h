@@ -286,6 +286,70 @@ int mirec_sweep_groups(int32_t dim);
 int mirec_propagate_sweep(const mirec_csr_t *csr, const mirec_prop_t *p,
                           const mirec_sweep_t *sw, mirec_stream_t stream);
 
+/* Per-wave form of the column-sweep layout, for a block of CSR rows [row0,
+ * row0 + n_rows) whose columns all lie in the source block [src0, src0 +
+ * n_src) (a bipartite graph's item rows: src0 = 0; its user rows: src0 =
+ * n_users).  Tiles of tile_rows consecutive rows as in mirec_sweep_t; a
+ * tile's rows are cut into MIREC_SWEEP_WAVES runs of wave_rows = ceil(tile_rows
+ * / MIREC_SWEEP_WAVES) consecutive rows, one wave of the workgroup each.
+ * Stream s = tile * MIREC_SWEEP_WAVES + wave occupies slot[wptr[s], wptr[s + 1])
+ * and holds all entries of its rows merged in (column, CSR position) order as
+ * 8-byte slots (local row << 32) | column (column as in the CSR, local row
+ * inside the tile).  Slots come in steps of 4 (one per 16-lane group) and
+ * batches of 4 steps; a stream is a whole number of batches.  The slots of a
+ * step name different rows or are padding: local row -1 and the column of
+ * the real slot before it.  Steps are filled greedily from the merged order:
+ * a step takes, among the pending entries less than MIREC_SWEEP_LOOKAHEAD
+ * merged positions past the oldest pending one, the earliest whose row the
+ * step does not hold yet, so an entry never overtakes an earlier entry of
+ * its row and per row the columns ascend with duplicate edges in CSR order.
+ * `grid` workgroups take the tiles b, b + grid, ... in turn.  All pointers
+ * are device pointers. */
+#define MIREC_SWEEP_WAVES 8
+#define MIREC_SWEEP_LOOKAHEAD 16
+#define MIREC_SWEEP_BATCH 16 /* slots: 4 steps of 4 */
+
+typedef struct mirec_sweep_wave {
+  int64_t row0;
+  int64_t n_rows;
+  int64_t src0;
+  int64_t n_src;
+  int64_t n_slots; /* wptr[n_tiles * MIREC_SWEEP_WAVES], > 0 */
+  int32_t tile_rows;
+  int32_t wave_rows;
+  int32_t n_tiles;
+  int32_t band_rows;
+  int32_t grid; /* workgroups launched, 1 .. n_tiles */
+  int32_t _pad;
+  const int64_t *wptr; /* [n_tiles * MIREC_SWEEP_WAVES + 1], in slots */
+  const int64_t *slot; /* [n_slots] */
+} mirec_sweep_wave_t;
+
+size_t mirec_sweep_wave_sizeof(void);
+
+/* Host: fill wptr [ceil(n_rows / tile_rows) * MIREC_SWEEP_WAVES + 1] and
+ * *n_slots (the padded length, which depends on the data) from the host CSR,
+ * and slot[0, *n_slots) when slot_cap >= *n_slots.  MIREC_ERR_WORKSPACE if
+ * slot_cap is smaller (wptr and *n_slots are valid: call again with room;
+ * slot may be NULL with slot_cap 0 as a size query); MIREC_ERR_RANGE if an
+ * entry's column is outside [src0, src0 + n_src). */
+int mirec_sweep_wave_build(const int64_t *rowptr, const int32_t *col, int64_t row0,
+                           int64_t n_rows, int64_t src0, int64_t n_src,
+                           int32_t tile_rows, int64_t *wptr, int64_t *slot,
+                           int64_t slot_cap, int64_t *n_slots);
+
+/* mirec_propagate_sweep with the per-wave layout `items` (the tail rows of
+ * the CSR, as `sw` there).  The rows [0, items->row0) go through the row
+ * kernel, or, when `users` is a layout of exactly these rows, through the
+ * sweep kernel too (a second launch on the same stream; no row kernel runs).
+ * Same qualifying rule; anything else (items == NULL included) is exactly
+ * mirec_propagate.  Per row the sum runs in ascending source column, one
+ * term at a time: for the rows of `items` bitwise equal to
+ * mirec_propagate_sweep's. */
+int mirec_propagate_sweep_wave(const mirec_csr_t *csr, const mirec_prop_t *p,
+                               const mirec_sweep_wave_t *items,
+                               const mirec_sweep_wave_t *users, mirec_stream_t stream);
+
 /* out[e] = sum_c a[row(e), c] * b[col[e], c] for every entry e of the CSR, in
  * CSR order (row(e) = the row whose range holds e): with a = dL/dy and b = x
  * the gradient of y = A x with respect to the entry values (csr->val itself

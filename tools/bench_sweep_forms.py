@@ -1,0 +1,92 @@
+"""One full PRESCALED launch (forward layer 1's arguments, unpruned) of
+LightGCN d = 64 on the bench.py C2 graph in the forms of the column sweep:
+
+  row          the row kernel for every row (use_sweep = False)
+  group        item rows by the group form of the sweep
+  wave         item rows by the wave form (§14), user rows by the row kernel
+  wave+users   both blocks by the wave form
+
+and, with --sizes, the wave form at other (tile_rows, band_rows).  The forms
+alternate inside one process; each figure is the median of --reps device-event
+timings after --warmup launches.  Prints one JSON line per form.
+
+  python tools/bench_sweep_forms.py [--reps 10] [--sizes items:196x2048,...]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--users", type=int, default=1_000_000)
+    ap.add_argument("--items", type=int, default=100_000)
+    ap.add_argument("--edges", type=int, default=20_000_000)
+    ap.add_argument("--sizes", default="",
+                    help="comma list of block:TILExBAND, block = items or users")
+    args = ap.parse_args()
+    from furusato_recommend_amd import SyntheticBipartite
+    from furusato_recommend_amd._lib import IN_PRESCALED
+    from furusato_recommend_amd.engine import PropagationEngine
+    from furusato_recommend_amd.graph import Graph
+    dev = torch.device("cuda:0")
+    ds = SyntheticBipartite(args.users, args.items, args.edges, seed=0)
+    g = Graph.from_interactions(ds.trainUser, ds.trainItem, ds.n_users, ds.m_items, dev)
+    D = 64
+    forms = {"row": {"use_sweep": False}, "group": {"sweep_form": "group"},
+             "wave": {"sweep_form": "wave", "sweep_users": False},
+             "wave+users": {"sweep_form": "wave", "sweep_users": True}}
+    engines = {}
+    for name, sw in forms.items():
+        engines[name] = (PropagationEngine(g, D, 3, 2048), sw, None)
+    for spec in filter(None, args.sizes.split(",")):
+        block, size = spec.split(":")
+        tile, band = (int(v) for v in size.split("x"))
+        eng = PropagationEngine(g, D, 3, 2048)
+        sw = {"sweep_form": "wave", "sweep_users": block == "users"}
+        engines[spec] = (eng, sw, {"wave_" + block: (tile, band)})
+    for name, (eng, sw, sizes) in engines.items():
+        for k, v in sw.items():
+            setattr(eng, k, v)
+        if sizes:
+            eng.set_sweep_sizes(**sizes)
+    x = torch.randn(g.n_nodes, D, device=dev) * 0.1
+    add = torch.randn(g.n_nodes, D, device=dev) * 0.1
+    out, xs = torch.empty_like(x), torch.empty_like(x)
+    times = {k: [] for k in engines}
+    for it in range(args.warmup + args.reps):
+        for name, (eng, _, _) in engines.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            eng._prop(in_mode=IN_PRESCALED, x_in=x, addend=add, out=out, xs_out=xs)
+            e.record()
+            e.synchronize()
+            if it >= args.warmup:
+                times[name].append(s.elapsed_time(e))
+    for name, (eng, sw, _) in engines.items():
+        ts = sorted(times[name])
+        res = {"form": name, "ms_median": round(statistics.median(ts), 4),
+               "ms_min": round(ts[0], 4), "ms_max": round(ts[-1], 4)}
+        if sw.get("sweep_form") == "wave":
+            for blk, lay in (("items", eng.sweep_wave),
+                             ("users", eng.sweep_wave_users if eng.sweep_users else None)):
+                if lay is not None:
+                    d = lay.desc
+                    res[blk] = {"tile_rows": d.tile_rows, "band_rows": d.band_rows,
+                                "tiles": d.n_tiles, "grid": d.grid,
+                                "passes": -(-d.n_tiles // d.grid), "slots": d.n_slots,
+                                "pad_share": round(1 - lay.n_entries / d.n_slots, 4)}
+        print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()

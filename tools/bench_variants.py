@@ -25,6 +25,11 @@ VARIANTS = {
     "no_reuse": {"reuse_prescaled": False},
     "mask_only": {"use_hop_list": False, "reuse_prescaled": False},
     "no_sweep": {"use_sweep": False},
+    # the column sweep's forms: a stream per lane group, a
+    # stream per wave for the item rows, and the wave form for both blocks
+    "sweep_group": {"sweep_form": "group", "sweep_users": False},
+    "sweep_wave": {"sweep_form": "wave", "sweep_users": False},
+    "sweep_wave_users": {"sweep_form": "wave", "sweep_users": True},
 }
 
 
@@ -61,6 +66,7 @@ def main():
         eng.train_step(emb, model.optim, u, p, n, 1e-4)
 
     for name in args.variants.split(","):
+        defaults = {k: getattr(eng, k) for k in VARIANTS[name]}
         for k, v in VARIANTS[name].items():
             setattr(eng, k, v)
         eng.invalidate_prescaled()
@@ -81,8 +87,8 @@ def main():
             launches.append(round(sum(ms) / len(ms), 4))
         print(json.dumps({"variant": name, "ms_per_step": round(dt * 1e3, 4),
                           "launch_ms": launches, "prop_sum_ms": round(sum(launches), 4)}))
-        for k in VARIANTS[name]:
-            setattr(eng, k, True)
+        for k, v in defaults.items():
+            setattr(eng, k, v)
 
 
 if __name__ == "__main__":
