@@ -63,6 +63,7 @@ class Prop(Structure):
         ("row_count", c_void_p),
         ("row_list_cap", c_int64), ("narrow_max", c_int32), ("_pad2", c_int32),
         ("wide_list", c_void_p), ("wide_count", c_void_p),
+        ("scale_src", c_void_p), ("scale_dst", c_void_p), ("scale_next", c_void_p),
     ]
 
 

@@ -36,6 +36,13 @@
 // earlier ones, instruction for instruction.
 // mirec_edge_dot gives the gradient with respect to the values.
 //
+// Scales (mirec_prop_t scale_src / scale_dst / scale_next, optional): dinv
+// plays three roles, the scale of a gathered neighbour (RAW, SPARSE), of the
+// row sum, and of the row written for the next layer; a launch that names any
+// of them runs the kScaled instantiations, which read the three from their
+// own vectors (D^-(1-r) A D^-r and its transpose, model/radj.py:28-44).  The
+// other instantiations are the earlier ones, instruction for instruction.
+//
 // Epilogue (per row, LPR lanes): z = dinv_i * sum + seed[slot_i];
 // xs_out = dinv_i * z (next layer's pre-scaled input);
 // o = (z + addend)/divisor + seed2[slot_i]; out = o or Adam(param; grad=o).
@@ -76,11 +83,17 @@ struct PropK {
   const int32_t *wide_list;  // rows gathered by a whole workgroup each (list mode)
   const int32_t *wide_count;
   const float *val;          // [nnz] per-entry weight (WEIGHTED instantiations only)
+  // SCALED instantiations only (there `dinv` above is the row sum's scale):
+  const float *scale_src;    // [n_rows] scale of a gathered neighbour (RAW, SPARSE)
+  const float *scale_next;   // [n_rows] scale of the row written to xs_out
 };
 
 // prop_kernel's MODE argument with this bit set is the edge-weighted walk
 // (the unweighted instantiations keep their names: MODE 0..3).
 constexpr int kWeighted = 4;
+// ... and with this bit the three scales come from their own vectors
+// (never together with kWeighted: refused by the host).
+constexpr int kScaled = 8;
 
 __device__ __forceinline__ bool bit_set(const uint8_t *bm, int64_t i) { return bm[i] != 0; }
 
@@ -103,7 +116,9 @@ __device__ __forceinline__ bool bit_set(const uint8_t *bm, int64_t i) { return b
 // to its column and follows it through the compaction, and the per-neighbour
 // weight becomes val (PRESCALED, which then takes the fma form) or
 // val * dinv_j (RAW, SPARSE).  Same order of terms as the unweighted sum.
-template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED, bool NARROW>
+// SCALED: the neighbour's scale is scale_src_j instead of dinv_j.
+template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED, bool NARROW,
+          bool SCALED = false>
 __device__ __forceinline__ float4 gather(const PropK &a, int64_t beg, int64_t end, int lane) {
   constexpr int LPR = D / 4;
   constexpr int G = 64 / LPR;
@@ -146,7 +161,7 @@ __device__ __forceinline__ float4 gather(const PropK &a, int64_t beg, int64_t en
     else if (!slot_filter) myr = me < cnt ? a.slot[myc] : 0;
     float myw = 1.f;
     if (MODE == MIREC_IN_RAW || MODE == MIREC_IN_SPARSE) {
-      if (me < cnt) myw = a.dinv[myc];
+      if (me < cnt) myw = SCALED ? a.scale_src[myc] : a.dinv[myc];
     }
     if (WEIGHTED) myw = me < cnt ? myv * myw : 0.f;
     if (MODE == MIREC_IN_SPARSE && myr < 0) {  // byte map set without a seed row
@@ -188,15 +203,19 @@ __device__ __forceinline__ float4 combine_groups(float4 s) {
   return s;
 }
 
-template <int D>
+// SCALED: a.dinv is the row sum's scale (set so by the host) and the row
+// written to xs_out is scaled by scale_next instead.
+template <int D, bool SCALED = false>
 __device__ __forceinline__ void row_epilogue(const PropK &a, int64_t row, float4 s, int sub) {
   const float di = a.dinv[row];
+  float dn = di;
+  if (SCALED && a.xs_out != nullptr) dn = a.scale_next[row];
   const int64_t off = row * D + sub * 4;
   float4 z = f4_scale(di, s);
   int sl = -1;
   if (a.slot != nullptr && (a.seed != nullptr || a.seed2 != nullptr)) sl = a.slot[row];
   if (a.seed != nullptr && sl >= 0) z = f4_add(z, ld4(a.seed + (int64_t)sl * D + sub * 4));
-  if (a.xs_out != nullptr && a.param == nullptr) st4(a.xs_out + off, f4_scale(di, z));
+  if (a.xs_out != nullptr && a.param == nullptr) st4(a.xs_out + off, f4_scale(dn, z));
   if (a.out == nullptr && a.param == nullptr) return;
   if (a.out_mask != nullptr && a.param == nullptr && a.out_mask[row] == 0) return;
   float4 o = z;
@@ -218,7 +237,7 @@ __device__ __forceinline__ void row_epilogue(const PropK &a, int64_t row, float4
     st4(a.v + off, v);
     if (a.out != nullptr) st4(a.out + off, o);
     // with Adam, xs_out receives the pre-scaled UPDATED parameter
-    if (a.xs_out != nullptr) st4(a.xs_out + off, f4_scale(di, p));
+    if (a.xs_out != nullptr) st4(a.xs_out + off, f4_scale(dn, p));
   } else {
     st4(a.out + off, o);
   }
@@ -236,7 +255,7 @@ constexpr int kWavesPerBlock = 4;
 // short list does not pay for its host-side capacity in empty waves.
 // MASKED = in_mask filter on neighbours, ROWMASK = row_mask filter on rows
 // (separate instantiations so profiles tell full and pruned launches apart).
-template <int D, int UNROLL, int MODE, bool MASKED, bool ROWMASK, bool WEIGHTED>
+template <int D, int UNROLL, int MODE, bool MASKED, bool ROWMASK, bool WEIGHTED, bool SCALED>
 __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nrows,
                                           int64_t row_waves) {
   constexpr int LPR = D / 4;
@@ -262,8 +281,8 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
     }
     const int64_t deg = have ? end - beg : 0;
     if (G > 1 && __ballot(deg > a.narrow_max) == 0ull) {
-      float4 s = gather<D, NARROW_UNROLL, MODE, MASKED, WEIGHTED, true>(a, beg, end, lane);
-      if (have) row_epilogue<D>(a, row, s, sub);
+      float4 s = gather<D, NARROW_UNROLL, MODE, MASKED, WEIGHTED, true, SCALED>(a, beg, end, lane);
+      if (have) row_epilogue<D, SCALED>(a, row, s, sub);
       return;
     }
 #pragma unroll 1
@@ -273,9 +292,9 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
       const int32_t r = __shfl(row, src);
       const int64_t rb = __shfl((long long)beg, src);
       const int64_t re = __shfl((long long)end, src);
-      float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false>(a, rb, re, lane);
+      float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED>(a, rb, re, lane);
       s = combine_groups<D>(s);
-      if (lane < LPR) row_epilogue<D>(a, r, s, sub);
+      if (lane < LPR) row_epilogue<D, SCALED>(a, r, s, sub);
     }
   } else {
     const int64_t sg = w - row_waves;
@@ -284,7 +303,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
     if (ROWMASK && !bit_set(a.row_mask, row)) return;
     const int64_t beg = a.seg_beg[sg];
     const int64_t end = min(beg + (int64_t)a.split, a.rowptr[row + 1]);
-    float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false>(a, beg, end, lane);
+    float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED>(a, beg, end, lane);
     s = combine_groups<D>(s);
     if (lane < LPR) st4(a.partial + sg * D + sub * 4, s);
   }
@@ -294,7 +313,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
 // quarter of the row's entries, the four wave sums are added in wave order
 // through LDS (deterministic), wave 0 runs the epilogue.  Block-uniform
 // control flow (contains barriers).
-template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED>
+template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED, bool SCALED>
 __device__ __forceinline__ void block_row(const PropK &a, int32_t row) {
   constexpr int LPR = D / 4;
   __shared__ float4 red[kWavesPerBlock - 1][LPR];
@@ -305,28 +324,28 @@ __device__ __forceinline__ void block_row(const PropK &a, int32_t row) {
   if (a.split > 0 && end - beg > a.split) return;  // segments handle it (uniform)
   const int64_t q = (end - beg + kWavesPerBlock - 1) / kWavesPerBlock;
   const int64_t wb = min(beg + wid * q, end), we = min(wb + q, end);
-  float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false>(a, wb, we, lane);
+  float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED>(a, wb, we, lane);
   s = combine_groups<D>(s);
   if (wid > 0 && lane < LPR) red[wid - 1][sub] = s;
   __syncthreads();
   if (wid == 0 && lane < LPR) {
 #pragma unroll
     for (int k = 0; k < kWavesPerBlock - 1; ++k) s = f4_add(s, red[k][sub]);
-    row_epilogue<D>(a, row, s, sub);
+    row_epilogue<D, SCALED>(a, row, s, sub);
   }
   __syncthreads();  // red[] is reused by the block's next row
 }
 
 // One row gathered by one wave.
-template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED>
+template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED, bool SCALED>
 __device__ __forceinline__ void wave_row(const PropK &a, int32_t row) {
   constexpr int LPR = D / 4;
   const int lane = threadIdx.x & 63;
   const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
   if (a.split > 0 && end - beg > a.split) return;  // segments handle it
-  float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false>(a, beg, end, lane);
+  float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED>(a, beg, end, lane);
   s = combine_groups<D>(s);
-  if (lane < LPR) row_epilogue<D>(a, row, s, lane % LPR);
+  if (lane < LPR) row_epilogue<D, SCALED>(a, row, s, lane % LPR);
 }
 
 // Grid of the list launches (their row counts live on the device): 4x the
@@ -337,17 +356,19 @@ constexpr int64_t kListBlocks = 8192;
 
 // Occupancy floor (waves per SIMD): keeps the register allocator at <= 72
 // VGPRs so 7-8 waves per SIMD keep enough gathers in flight.
-// MODE_W = in_mode, + kWeighted for an edge-weighted launch (csr->val).
+// MODE_W = in_mode, + kWeighted for an edge-weighted launch (csr->val), or
+// + kScaled for a launch with scale vectors of its own.
 template <int D, int UNROLL, int MODE_W, bool MASKED, bool ROWMASK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8)))
 MIREC_NO_PK_F32 void prop_kernel(PropK a) {
   constexpr int MODE = MODE_W & 3;
   constexpr bool WEIGHTED = (MODE_W & kWeighted) != 0;
+  constexpr bool SCALED = (MODE_W & kScaled) != 0;
   constexpr int G = 64 / (D / 4);
   // wave index made provably uniform (SGPR): loop control stays scalar
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (!ROWMASK || a.row_list == nullptr) {
-    prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED>(
+    prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED, SCALED>(
         a, (int64_t)blockIdx.x * kWavesPerBlock + wid, a.n_rows, a.row_waves);
     return;
   }
@@ -368,15 +389,15 @@ MIREC_NO_PK_F32 void prop_kernel(PropK a) {
   for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
     if (b < wide_blocks) {
       if constexpr (WPB == 1) {
-        block_row<D, UNROLL, MODE, MASKED, WEIGHTED>(a, a.wide_list[b]);
+        block_row<D, UNROLL, MODE, MASKED, WEIGHTED, SCALED>(a, a.wide_list[b]);
       } else {
         const int64_t i = b * WPB + wid;
-        if (i < n_wide) wave_row<D, UNROLL, MODE, MASKED, WEIGHTED>(a, a.wide_list[i]);
+        if (i < n_wide) wave_row<D, UNROLL, MODE, MASKED, WEIGHTED, SCALED>(a, a.wide_list[i]);
       }
     } else {
       const int64_t w = (b - wide_blocks) * kWavesPerBlock + wid;
       if (w < waves)
-        prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED>(a, w, nrows, row_waves);
+        prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED, SCALED>(a, w, nrows, row_waves);
     }
   }
 }
@@ -387,7 +408,7 @@ MIREC_NO_PK_F32 void prop_kernel(PropK a) {
 // fixed two-level order (deterministic); a Zipf hub row of 800 segments is
 // 50 loads deep per group instead of a serial walk of 800 dependent loads
 // (258 -> ~15 us per launch on the C2 Zipf graph).
-template <int D>
+template <int D, bool SCALED>
 __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void prop_finalize(PropK a, const int32_t *long_rows,
                                                      const int64_t *long_segptr, int64_t n_long) {
   constexpr int LPR = D / 4;
@@ -418,7 +439,7 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void prop_finalize(PropK a, co
   float4 t = red[0][sub];
 #pragma unroll
   for (int k = 1; k < NG; ++k) t = f4_add(t, red[k][sub]);
-  row_epilogue<D>(a, row, t, sub);
+  row_epilogue<D, SCALED>(a, row, t, sub);
 }
 
 // ---- column sweep (mirec_sweep_t): the item rows of a full PRESCALED launch.
@@ -456,7 +477,7 @@ struct SweepK {
   int32_t n_bands;
 };
 
-template <int D, int U>
+template <int D, int U, bool SCALED>
 __device__ __forceinline__ void sweep_work(const PropK &a, const SweepK &s) {
   constexpr int LPR = D / 4;
   static_assert(LPR % U == 0 && LPR <= 64, "a chunk of LPR entries is U-row batches");
@@ -558,16 +579,16 @@ __device__ __forceinline__ void sweep_work(const PropK &a, const SweepK &s) {
   }
   // rows are private to their group (same lanes wrote and read them)
   for (int lr = lr0; lr < lr1; ++lr)
-    row_epilogue<D>(a, s.row0 + tile_row0 + lr, sweep_acc[lr * LPR + sub], sub);
+    row_epilogue<D, SCALED>(a, s.row0 + tile_row0 + lr, sweep_acc[lr * LPR + sub], sub);
 }
 
 // (the body is a separate always-inline function: the shuffle and ballot
 // wrappers inline into it, and it into the kernel, across the kernel's
 // packed-f32 target attribute)
-template <int D, int U>
+template <int D, int U, bool SCALED>
 __global__ __launch_bounds__(kSweepThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 MIREC_NO_PK_F32 void prop_sweep_kernel(PropK a, SweepK s) {
-  sweep_work<D, U>(a, s);
+  sweep_work<D, U, SCALED>(a, s);
 }
 
 // ---- per-wave form of the sweep (mirec_sweep_wave_t).  The four lane groups
@@ -602,7 +623,7 @@ struct SweepWaveK {
   int32_t n_bands;
 };
 
-template <int D, int U>
+template <int D, int U, bool SCALED>
 __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK &s) {
   constexpr int LPR = D / 4;
   constexpr int G = 64 / LPR;          // lane groups = slots per step
@@ -695,15 +716,15 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
     }
     // rows are private to their wave
     for (int lr = lr0 + g; lr < lr1; lr += G)
-      row_epilogue<D>(a, s.row0 + tile_row0 + lr, sweep_acc[lr * LPR + sub], sub);
+      row_epilogue<D, SCALED>(a, s.row0 + tile_row0 + lr, sweep_acc[lr * LPR + sub], sub);
     __syncthreads();  // the accumulators are reused by the workgroup's next tile
   }
 }
 
-template <int D, int U>
+template <int D, int U, bool SCALED>
 __global__ __launch_bounds__(kSweepThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 MIREC_NO_PK_F32 void prop_sweep_wave_kernel(PropK a, SweepWaveK s) {
-  sweep_wave_work<D, U>(a, s);
+  sweep_wave_work<D, U, SCALED>(a, s);
 }
 
 using PropFn = void (*)(PropK);
@@ -712,15 +733,17 @@ using PropFn = void (*)(PropK);
 // always filters: by slot >= 0 without an in_mask), NONE only unmasked and
 // unweighted (it reads no neighbours).  The cases stand in the order the
 // kernels have in the code object, which follows their first use here.
+// The kScaled cases come after all the earlier ones, so those keep their
+// places; scaled and weighted never meet (refused in propagate()).
 template <int D, int UNROLL>
-static PropFn prop_kernel_for(int mode, bool masked, bool rowmask, bool weighted) {
+static PropFn prop_kernel_for(int mode, bool masked, bool rowmask, bool weighted, bool scaled) {
   if (mode == MIREC_IN_SPARSE) masked = true;
   if (mode == MIREC_IN_NONE) weighted = false;
 #define MIREC_PROP_CASE(MODE_W, MASKED)                               \
   case (MODE_W) * 2 + (MASKED):                                       \
     return rowmask ? prop_kernel<D, UNROLL, (MODE_W), MASKED, true>   \
                    : prop_kernel<D, UNROLL, (MODE_W), MASKED, false>;
-  switch ((mode | (weighted ? kWeighted : 0)) * 2 + masked) {
+  switch ((mode | (weighted ? kWeighted : 0) | (scaled ? kScaled : 0)) * 2 + masked) {
     MIREC_PROP_CASE(MIREC_IN_PRESCALED | kWeighted, false)
     MIREC_PROP_CASE(MIREC_IN_PRESCALED, false)
     MIREC_PROP_CASE(MIREC_IN_PRESCALED | kWeighted, true)
@@ -731,6 +754,12 @@ static PropFn prop_kernel_for(int mode, bool masked, bool rowmask, bool weighted
     MIREC_PROP_CASE(MIREC_IN_RAW, true)
     MIREC_PROP_CASE(MIREC_IN_SPARSE | kWeighted, true)
     MIREC_PROP_CASE(MIREC_IN_SPARSE, true)
+    MIREC_PROP_CASE(MIREC_IN_PRESCALED | kScaled, false)
+    MIREC_PROP_CASE(MIREC_IN_PRESCALED | kScaled, true)
+    MIREC_PROP_CASE(MIREC_IN_RAW | kScaled, false)
+    MIREC_PROP_CASE(MIREC_IN_RAW | kScaled, true)
+    MIREC_PROP_CASE(MIREC_IN_SPARSE | kScaled, true)
+    MIREC_PROP_CASE(MIREC_IN_NONE | kScaled, false)
     default:  // in_mask is refused with NONE (mirec_propagate_sweep)
     MIREC_PROP_CASE(MIREC_IN_NONE, false)
   }
@@ -750,14 +779,15 @@ static int launch_prop(const mirec_csr_t *c, PropK k, int64_t list_cap, int mode
     blocks = std::min(blocks, kListBlocks);
   }
   if (blocks > 0) {
-    const PropFn kernel = prop_kernel_for<D, UNROLL>(mode, k.in_mask != nullptr,
-                                                     k.row_mask != nullptr, k.val != nullptr);
+    const PropFn kernel =
+        prop_kernel_for<D, UNROLL>(mode, k.in_mask != nullptr, k.row_mask != nullptr,
+                                   k.val != nullptr, k.scale_next != nullptr);
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, k);
     MIREC_LAUNCH_CHECK();
   }
   if (c->n_long > 0) {
-    hipLaunchKernelGGL((prop_finalize<D>), dim3((unsigned)c->n_long), dim3(256), 0, st, k,
-                       c->long_rows,
+    const auto fin = k.scale_next != nullptr ? prop_finalize<D, true> : prop_finalize<D, false>;
+    hipLaunchKernelGGL(fin, dim3((unsigned)c->n_long), dim3(256), 0, st, k, c->long_rows,
                        c->long_segptr, c->n_long);
     MIREC_LAUNCH_CHECK();
   }
@@ -908,8 +938,9 @@ static int launch_sweep(const mirec_csr_t *c, const PropK &k, const mirec_sweep_
   s.band_rows = sw->band_rows;
   s.n_bands = (int32_t)std::max<int64_t>(1, (sw->n_src + sw->band_rows - 1) / sw->band_rows);
   const size_t lds = (size_t)sw->tile_rows * D * sizeof(float);
-  hipLaunchKernelGGL((prop_sweep_kernel<D, 4>), dim3((unsigned)sw->n_tiles), dim3(kSweepThreads),
-                     lds, st, k, s);
+  const auto kernel =
+      k.scale_next != nullptr ? prop_sweep_kernel<D, 4, true> : prop_sweep_kernel<D, 4, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)sw->n_tiles), dim3(kSweepThreads), lds, st, k, s);
   MIREC_LAUNCH_CHECK();
   if (sw->row0 == 0) return MIREC_OK;
   return launch_head<D, UNROLL>(c, k, sw->row0, st);
@@ -944,8 +975,9 @@ static int launch_sweep_wave(const PropK &k, const mirec_sweep_wave_t *w, hipStr
   s.band_rows = w->band_rows;
   s.n_bands = (int32_t)std::max<int64_t>(1, (w->n_src + w->band_rows - 1) / w->band_rows);
   const size_t lds = (size_t)w->tile_rows * D * sizeof(float);
-  hipLaunchKernelGGL((prop_sweep_wave_kernel<D, 4>), dim3((unsigned)w->grid),
-                     dim3(kSweepThreads), lds, st, k, s);
+  const auto kernel = k.scale_next != nullptr ? prop_sweep_wave_kernel<D, 4, true>
+                                              : prop_sweep_wave_kernel<D, 4, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)w->grid), dim3(kSweepThreads), lds, st, k, s);
   MIREC_LAUNCH_CHECK();
   return MIREC_OK;
 }
@@ -1016,6 +1048,17 @@ static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sw
   k.wide_list = p->wide_list;
   k.wide_count = p->wide_count;
   k.val = c->val;
+  // A launch that names any scale runs the kScaled instantiations with all
+  // three resolved (NULL = csr->dinv); they carry no edge weights.
+  const bool scaled =
+      p->scale_src != nullptr || p->scale_dst != nullptr || p->scale_next != nullptr;
+  MIREC_CHECK_ARG(!scaled || c->val == nullptr);
+  k.scale_src = k.scale_next = nullptr;
+  if (scaled) {
+    k.scale_src = p->scale_src != nullptr ? p->scale_src : c->dinv;
+    k.dinv = p->scale_dst != nullptr ? p->scale_dst : c->dinv;
+    k.scale_next = p->scale_next != nullptr ? p->scale_next : c->dinv;
+  }
   const int64_t cap = p->row_list_cap;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (sweep_qualifies(c, p, sw)) return launch_sweep<64, 4>(c, k, sw, st);

@@ -199,7 +199,7 @@ class DataParallel:
             from . import _lib
             from ._lib import check, lib
             check(lib.mirec_shard_unpack(st.data_ptr(), N, D, W, self.rank, s0, s1 - s0,
-                                         _lib.ptr(None if x0s is None else self.engine.g.dinv),
+                                         _lib.ptr(None if x0s is None else self.engine._scale()),
                                          t.data_ptr(), _lib.ptr(x0s), _lib.stream_handle()),
                   "shard_unpack")
             return

@@ -15,10 +15,13 @@ launches with no host synchronisation:
   BPR      (3 + sort)     scores, softplus, loss; sorted (node, occurrence)
                           pairs → per-node gradient seeds d = dL/d out /(L+1)
                           and the reg-gradient seed.
-  backward (L launches)   Horner: g_L = d, g_l = d + Â g_{l+1} (Â symmetric:
+  backward (L launches)   Horner: g_L = d, g_l = d + Âᵀ g_{l+1} (Â symmetric:
                           the backward SpMM is the forward kernel on the
-                          same CSR).  The first backward layer gathers only
-                          the seeded neighbours (IN_SPARSE: slot[j] >= 0) and
+                          same CSR; with an r-adjusted graph, Graph.r != 0.5,
+                          Âᵀ is the same launch with the source and
+                          destination scales swapped, see _prop).  The first
+                          backward layer gathers only the seeded
+                          neighbours (IN_SPARSE: slot[j] >= 0) and
                           is written on F1 only; the second skips neighbours
                           outside F1; the last one adds the reg seed and
                           applies Adam to E in its epilogue, so the dense
@@ -50,9 +53,13 @@ SWEEP_USERS = True
 
 
 def prop_launch_bytes(in_mode: int, n_nodes: int, nnz: int, dim: int, *, slot=False,
-                      xs_out=False, addend=False, out=False, adam=False, weighted=False) -> int:
+                      xs_out=False, addend=False, out=False, adam=False, weighted=False,
+                      scaled=False) -> int:
     """Algorithmic HBM bytes of one mirec_propagate launch:
-    every operand the launch must read or write, each exactly once."""
+    every operand the launch must read or write, each exactly once.
+    ``scaled``: a launch with scale vectors of its own (r-adjusted graph)
+    whose xs_out scale differs from its row-sum scale reads a second
+    per-row scale."""
     N, D = n_nodes, dim
     row = N * D * 4
     b = (N + 1) * 8 + N * 4                       # rowptr (int64), dinv_i
@@ -66,6 +73,8 @@ def prop_launch_bytes(in_mode: int, n_nodes: int, nnz: int, dim: int, *, slot=Fa
         b += nnz * 4                              # the per-entry edge weight
     if slot:
         b += N * 4                                # slot_i
+    if scaled:
+        b += N * 4                                # the second per-row scale
     b += row * (int(xs_out) + int(addend) + int(out))
     if adam:
         b += 6 * row                              # param/m/v read + write
@@ -347,9 +356,24 @@ class PropagationEngine:
     def _prop(self, *, in_mode, x_in=None, seed_in=None, seed=None, addend=None, seed2=None,
               divisor=1.0, out=None, xs_out=None, adam=None, param=None, graph=None,
               row_mask=None, in_mask=None, row_list=None, row_count=None, row_list_cap=0,
-              out_mask=None, wide_list=None, wide_count=None):
+              out_mask=None, wide_list=None, wide_count=None, direction="fwd"):
+        """One propagation launch.  ``direction`` matters on an r-adjusted
+        graph only (scales a = deg^-r, b = deg^-(1-r); otherwise the three
+        scale pointers stay NULL = dinv): "fwd" applies Â = D_b A D_a and
+        writes xs_out = a ⊙ z; "bwd" applies Âᵀ = D_a A D_b and writes
+        xs_out = b ⊙ z; "bwd_last" is "bwd" whose xs_out is the next
+        FORWARD's input again (a ⊙ the updated table)."""
         g = graph or self.g
         p = Prop()
+        if g.scale_src is not None:
+            a, b = g.scale_src.data_ptr(), g.scale_dst.data_ptr()
+            if direction == "fwd":
+                p.scale_src, p.scale_dst, p.scale_next = a, b, a
+            elif direction in ("bwd", "bwd_last"):
+                p.scale_src, p.scale_dst = b, a
+                p.scale_next = a if direction == "bwd_last" else b
+            else:
+                raise ValueError(f"direction: 'fwd', 'bwd' or 'bwd_last', got {direction!r}")
         p.dim = self.dim
         p.in_mode = in_mode
         p.x_in = ptr(x_in)
@@ -409,7 +433,9 @@ class PropagationEngine:
                                  slot=bool(p.slot and (p.seed or p.seed2)),
                                  xs_out=bool(p.xs_out), addend=bool(p.addend) and not om,
                                  out=bool(p.out) and not om, adam=bool(p.param),
-                                 weighted=g.val is not None)
+                                 weighted=g.val is not None,
+                                 scaled=bool(p.scale_next) and bool(p.xs_out)
+                                 and p.scale_next != p.scale_dst)
 
     def compute_frontier(self, users=None, pos=None, neg=None, keys=None, n_keys: int = 0):
         """bm_self = S, bm_hop = S ∪ N(S) for a triple batch or a key list;
@@ -541,7 +567,8 @@ class PropagationEngine:
             self.seed_dense = torch.zeros(self.g.n_nodes, self.dim, dtype=torch.float32,
                                           device=self.g.device)
         check(lib.mirec_seed_dense(self.self_list.data_ptr(), self.self_count.data_ptr(),
-                                   self._self_cap, self.slot.data_ptr(), self.g.dinv.data_ptr(),
+                                   self._self_cap, self.slot.data_ptr(),
+                                   self._scale(backward=True).data_ptr(),
                                    seed_p.data_ptr(), self.dim, self.seed_dense.data_ptr(),
                                    int(clear), _lib.stream_handle()), "seed_dense")
         return self.seed_dense
@@ -595,8 +622,17 @@ class PropagationEngine:
         self._x0s_token = self._token(emb)
         self._acc_full = None
 
+    def _scale(self, backward: bool = False) -> torch.Tensor:
+        """The scale of a pre-scaled chain's rows: dinv, or on an r-adjusted
+        graph a = deg^-r (forward: x~ = a ⊙ x) / b = deg^-(1-r) (backward:
+        g~ = b ⊙ g)."""
+        g = self.g
+        if g.scale_src is None:
+            return g.dinv
+        return g.scale_dst if backward else g.scale_src
+
     def prescale(self, x: torch.Tensor, out: torch.Tensor):
-        check(lib.mirec_prescale(x.data_ptr(), self.g.dinv.data_ptr(), self.g.n_nodes, self.dim,
+        check(lib.mirec_prescale(x.data_ptr(), self._scale().data_ptr(), self.g.n_nodes, self.dim,
                                  out.data_ptr(), _lib.stream_handle()), "prescale")
 
     # ------------------------------------------------------------- forward
@@ -651,9 +687,12 @@ class PropagationEngine:
         self._prop(in_mode=IN_RAW, x_in=x, out=out, graph=graph)
 
     def propagate_accumulate(self, g_in: torch.Tensor, addend: torch.Tensor,
-                             out: torch.Tensor, graph: Graph | None = None):
-        """out = Â g_in + addend (generic autograd backward, dense seed)."""
-        self._prop(in_mode=IN_RAW, x_in=g_in, addend=addend, out=out, graph=graph)
+                             out: torch.Tensor, graph: Graph | None = None,
+                             transposed: bool = False):
+        """out = Â g_in + addend (generic autograd backward, dense seed);
+        ``transposed``: Âᵀ g_in + addend (the same on a graph without r)."""
+        self._prop(in_mode=IN_RAW, x_in=g_in, addend=addend, out=out, graph=graph,
+                   direction="bwd" if transposed else "fwd")
 
     # ------------------------------------------------------------------ BPR
     def bpr(self, out: torch.Tensor, emb: torch.Tensor, users, pos, neg, decay: float,
@@ -731,7 +770,7 @@ class PropagationEngine:
     # ------------------------------------------------------------- backward
     def backward(self, emb: torch.Tensor, adam: AdamState | None = None,
                  grad_out: torch.Tensor | None = None, last_rows=None, on_chunk=None):
-        """Horner backward from the current seeds (g_L = d, g_l = d + Â g_{l+1}).
+        """Horner backward from the current seeds (g_L = d, g_l = d + Âᵀ g_{l+1}).
 
         With ``adam`` the last layer applies Adam to ``emb`` in place (fused);
         otherwise the dense gradient dLoss/dE is written to ``grad_out``.
@@ -749,7 +788,7 @@ class PropagationEngine:
         L = self.L
         seed_p, seed_e, keys_sorted, n_keys = self._seeds
         hp = adam.next_hparams() if adam is not None else None
-        final = dict(seed2=seed_e)
+        final = dict(seed2=seed_e, direction="bwd_last")
         if adam is not None:
             final.update(adam=(adam, hp), param=emb)
             if L > 0 and self.reuse_prescaled:  # the update also emits the next x~_0
@@ -786,7 +825,7 @@ class PropagationEngine:
                     last_layer(**kw)
                 else:
                     kw.update(xs_out=self.xs[(L - 1 - l) % 2])
-                    self._prop(**kw)
+                    self._prop(**kw, direction="bwd")
         if self.sparse_filter == "dense" and L > 0:
             self._dense_seeds(seed_p, 1)
         check(lib.mirec_bpr_seed_reset(self.slot.data_ptr(), keys_sorted.data_ptr(), n_keys,
@@ -838,7 +877,7 @@ def edge_dot(graph: Graph, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor):
 def propagate(graph: Graph, x: torch.Tensor, out: torch.Tensor):
     """out = Â x on ``graph`` (one LGConv call; x, out: contiguous fp32
     [n_nodes, D] device tensors, D in SUPPORTED_DIMS; edge-weighted when the
-    graph carries values)."""
+    graph carries values, r-adjusted when it carries scales)."""
     n, D = x.shape
     if D not in _lib.SUPPORTED_DIMS or n != graph.n_nodes or out.shape != x.shape:
         raise ValueError(f"propagate: x {tuple(x.shape)}, out {tuple(out.shape)}, "
@@ -853,6 +892,9 @@ def propagate(graph: Graph, x: torch.Tensor, out: torch.Tensor):
     p.out = out.data_ptr()
     p.partial = ptr(graph.partial_buffer(D))
     p.narrow_max = 64
+    if graph.scale_src is not None:
+        p.scale_src = graph.scale_src.data_ptr()
+        p.scale_dst = graph.scale_dst.data_ptr()
     check(lib.mirec_propagate(graph.csr_ptr(), ctypes.byref(p), _lib.stream_handle()),
           "propagate")
 

@@ -96,6 +96,25 @@ def _weighted_dinv(dst: np.ndarray, w: np.ndarray, n_nodes: int) -> np.ndarray:
     return np.where(deg > 0, 1.0 / np.sqrt(np.where(deg > 0, deg, 1.0)), 0.0).astype(np.float32)
 
 
+def radj_scales(rowptr, r: float):
+    """The two per-node scales of rAdjConv (model/radj.py:28-44),
+    y_i = Σ_{(j→i)} x_j / (deg_j^r · deg_i^(1−r)): returns float32 arrays
+    ``(a, b)`` with a = deg^−r (the source scale of the forward) and
+    b = deg^−(1−r) (its destination scale), deg = the CSR row length
+    (multi-edges counted), both 0 where deg = 0, like dinv.  Computed in
+    float64 and rounded once.  ValueError unless r is finite and in [0, 1]."""
+    r = float(r)
+    if not np.isfinite(r) or r < 0.0 or r > 1.0:
+        raise ValueError(f"r must be a finite number in [0, 1], got {r!r}")
+    rp = np.asarray(rowptr, dtype=np.int64)
+    deg = (rp[1:] - rp[:-1]).astype(np.float64)
+    pos = deg > 0
+    safe = np.where(pos, deg, 1.0)
+    a = np.where(pos, safe ** (-r), 0.0).astype(np.float32)
+    b = np.where(pos, safe ** (-(1.0 - r)), 0.0).astype(np.float32)
+    return a, b
+
+
 class Graph:
     """CSR of the normalised adjacency Â = D^-1/2 A D^-1/2 (A symmetric)."""
 
@@ -154,6 +173,12 @@ class Graph:
             self.perm = torch.from_numpy(perm).to(dev)
             self.csr.val = self.val.data_ptr()
         self.transpose = None  # set for non-symmetric graphs (from_edge_index)
+        # r-adjusted normalisation (from_interactions(r != 0.5)): the forward's
+        # source scale a = deg^-r and destination scale b = deg^-(1-r) on the
+        # device; None = both are dinv and every launch leaves its scale
+        # pointers NULL
+        self.r = 0.5
+        self.scale_src = self.scale_dst = None
         self.col_sorted = None
         self.pos_cdf = None  # weighted positives (set_positive_probs)
         if self.n_users > 0 and self.m_items > 0:
@@ -174,10 +199,21 @@ class Graph:
     # ------------------------------------------------------------------ build
     @classmethod
     def from_interactions(cls, train_user, train_item, n_users: int, m_items: int,
-                          device, split: int = DEFAULT_SPLIT, weight=None) -> "Graph":
+                          device, split: int = DEFAULT_SPLIT, weight=None,
+                          r: float = 0.5) -> "Graph":
         """trainUser / trainItem arrays (dataloader.py:93-124) → symmetric CSR.
         ``weight`` (one finite, non-negative value per interaction): both
-        directions of interaction e carry weight[e], degrees are weight sums."""
+        directions of interaction e carry weight[e], degrees are weight sums.
+        ``r`` (model/radj.py): the normalisation 1 / (deg_j^r · deg_i^(1−r));
+        0.5 is this very graph (nothing added), any other value in [0, 1]
+        adds the two scale vectors of ``radj_scales`` (``scale_src``,
+        ``scale_dst``) and cannot be combined with ``weight``."""
+        r = float(r)
+        if not np.isfinite(r) or r < 0.0 or r > 1.0:
+            raise ValueError(f"r must be a finite number in [0, 1], got {r!r}")
+        if r != 0.5 and weight is not None:
+            raise ValueError("from_interactions: r != 0.5 cannot be combined with edge weights "
+                             "(the scaled kernels carry no values)")
         u = np.ascontiguousarray(np.asarray(train_user, dtype=np.int64))
         i = np.ascontiguousarray(np.asarray(train_item, dtype=np.int64))
         if u.shape != i.shape:
@@ -190,7 +226,13 @@ class Graph:
                                       int(m_items), rowptr.ctypes.data, col.ctypes.data,
                                       dinv.ctypes.data), "csr_bipartite")
         if weight is None:
-            return cls(rowptr, col, dinv, n_users, m_items, device, split)
+            g = cls(rowptr, col, dinv, n_users, m_items, device, split)
+            if r != 0.5:
+                a, b = radj_scales(rowptr, r)
+                g.r = r
+                g.scale_src = torch.from_numpy(a).to(g.device)
+                g.scale_dst = torch.from_numpy(b).to(g.device)
+            return g
         ne = u.shape[0]
         w = _check_weights(weight, ne, True, "from_interactions")
         # the CSR is the stable destination sort of the reference's doubled

@@ -13,6 +13,10 @@ Two execution paths, both on libmirec:
   * ``forward`` / ``bpr_loss`` — differentiable: propagation is an
     autograd.Function whose backward is the same HIP SpMM (Â is symmetric),
     for callers that build their own loss.
+
+``rAdjGCN`` (radj.py) is this class on a graph with the r-adjusted
+normalisation; ``LightGCN`` itself ignores ``config["r"]``, as the
+reference's 'lgn' does (model/lgcn.py never reads it).
 """
 from __future__ import annotations
 
@@ -41,7 +45,7 @@ class _Propagate(torch.autograd.Function):
         g = d
         for _ in range(L):
             nxt = torch.empty_like(d)
-            eng.propagate_accumulate(g, d, nxt)
+            eng.propagate_accumulate(g, d, nxt, transposed=True)
             g = nxt
         return g, None
 
@@ -54,7 +58,13 @@ def _config_get(config, *keys, default=None):
 
 
 class LightGCN(nn.Module):
-    """model/lgcn.py:44-151 on MI355X."""
+    """model/lgcn.py:44-151 on MI355X.  ``config["r"]`` is ignored here (the
+    reference's 'lgn' ignores it too): the normalisation is deg^-1/2 on both
+    sides; ``rAdjGCN`` is the model that reads it."""
+
+    def _graph_r(self, config) -> float:
+        """The r of the graph's normalisation 1 / (deg_j^r · deg_i^(1−r))."""
+        return 0.5
 
     def __init__(self, config: dict, dataset):
         super().__init__()
@@ -80,7 +90,7 @@ class LightGCN(nn.Module):
         self.graph = Graph.from_interactions(dataset.trainUser, dataset.trainItem,
                                              self.num_users, self.num_items, self.device,
                                              split=int(config.get("csr_split", DEFAULT_SPLIT)),
-                                             weight=weight)
+                                             weight=weight, r=self._graph_r(config))
         self.graph.set_positive_probs(positive_probs(config))
         self.__init_weight()
         self.optim = AdamState(self.all_embedding.weight, lr=config["lr"])

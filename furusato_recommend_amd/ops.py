@@ -37,7 +37,13 @@ _ids = itertools.count(1)
 
 
 def handle(graph) -> int:
-    """The operator handle of a graph.Graph (registered on first use)."""
+    """The operator handle of a graph.Graph (registered on first use).  The
+    operators are PyG's LGConv, which has no r: an r-adjusted graph
+    (``from_interactions(r != 0.5)``) is refused, its transpose is not its
+    own CSR."""
+    if getattr(graph, "scale_src", None) is not None:
+        raise ValueError("mirec operators: the graph carries r-adjusted scales "
+                         f"(r = {graph.r}); torch.ops.mirec.* propagate with deg^-1/2 only")
     h = getattr(graph, "_op_handle", None)
     if h is None or _graphs.get(h) is not graph:
         h = next(_ids)

@@ -356,7 +356,10 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(
         prog="python -m furusato_recommend_amd.train_dp",
         description="Data-parallel BPR training (ddp_lgcn.py / ddp_sage.py on MI355X)")
-    ap.add_argument("--model", default="lgn", help="registry name: lgn | sage | sasrec | mf")
+    ap.add_argument("--model", default="lgn",
+                    help="registry name: lgn | radj | sage | sasrec | mf")
+    ap.add_argument("--r", type=float, default=0.5,
+                    help="rAdjGCN's normalisation exponent (parse.py:49; read by --model radj)")
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one process per GPU)")
     ap.add_argument("--epochs", type=int, default=200, help="ddp_lgcn.py:667 range(200)")
     ap.add_argument("--bpr_batch", type=int, default=20000, help="per-rank batch (ddp_lgcn.py:646)")
@@ -440,7 +443,7 @@ def build_config(args, device: str) -> dict:
         "test_count": None if args.test_count < 0 else args.test_count,
         "train_iterative": args.train_iterative,
         "positive_num_limit": args.positive_num_limit, "seed": args.seed,
-        "suffix": args.suffix, "dp_mode": args.dp_mode,
+        "suffix": args.suffix, "dp_mode": args.dp_mode, "r": args.r,
         "checkpoint_path": os.path.join(args.path, f"ddp_{args.model}_{args.suffix}.pth"),
         **({"fanouts": list(ast.literal_eval(args.fanouts))} if args.fanouts else {}),
     }

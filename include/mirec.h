@@ -37,7 +37,9 @@ extern "C" {
 
 /* Still 1: mirec_csr_t gained a trailing field (`val`, the per-entry edge
  * weights) after the version was set; a binding checks its mirror of the
- * struct with mirec_struct_sizes, and a NULL `val` is the earlier behaviour. */
+ * struct with mirec_struct_sizes, and a NULL `val` is the earlier behaviour.
+ * Likewise mirec_prop_t's trailing scale_src / scale_dst / scale_next: NULL
+ * (each on its own) means csr->dinv, the earlier behaviour. */
 #define MIREC_ABI_VERSION 1
 
 enum mirec_status {
@@ -180,7 +182,16 @@ typedef struct mirec_adam_hparams {
  *   Adam(param_i, exp_avg_i, exp_avg_sq_i; grad = o_i)   (if param != NULL;
  *       then xs_out_i = dinv_i * param_i after the update)
  * `partial` is scratch of csr->n_seg * dim floats (may be NULL if n_seg==0).
- * Summation order per row is fixed by the CSR: results are deterministic. */
+ * Summation order per row is fixed by the CSR: results are deterministic.
+ *
+ * csr->dinv stands in three places above; scale_src / scale_dst / scale_next
+ * (optional, [n_rows] each, NULL = csr->dinv) replace it one place at a time:
+ *   xin~_j   = scale_src_j * x_j          (MIREC_IN_RAW, MIREC_IN_SPARSE)
+ *   y_i      = scale_dst_i * sum ...
+ *   xs_out_i = scale_next_i * z_i        (with Adam: scale_next_i * param_i)
+ * which gives D^-(1-r) A D^-r (rAdjConv, model/radj.py:28-44) and its
+ * transpose on the one symmetric CSR.  Every launch form honours them and
+ * the sweep still qualifies; with csr->val they are refused (MIREC_ERR_ARG). */
 typedef struct mirec_prop {
   int32_t dim;
   int32_t in_mode;
@@ -226,6 +237,10 @@ typedef struct mirec_prop {
                                the row, combined in LDS in a fixed order), so
                                a short list of long rows is not latency-bound */
   const int32_t *wide_count;
+  /* appended (see MIREC_ABI_VERSION); NULL = csr->dinv */
+  const float *scale_src;   /* [n_rows] scale of a gathered neighbour (modes 1/2) */
+  const float *scale_dst;   /* [n_rows] scale of the row sum */
+  const float *scale_next;  /* [n_rows] scale of z (or the updated param) for xs_out */
 } mirec_prop_t;
 
 int mirec_propagate(const mirec_csr_t *csr, const mirec_prop_t *p,
