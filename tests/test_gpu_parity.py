@@ -100,10 +100,16 @@ def test_autograd_path(golden, name):
     assert rel(m.all_embedding.weight, f["emb_step1"]) < TOL
 
 
-def test_engine_gradient_matches_reference(golden):
-    """Dense-gradient (data-parallel) variant of the fused backward."""
-    f = golden("lgcn_d64_L3.npz")
-    m = lgcn_from(f)
+@pytest.mark.parametrize("sparse_filter", ["slot", "bytemap", "dense"])
+@pytest.mark.parametrize("prune", [True, False])
+@pytest.mark.parametrize("name", LGCN)
+def test_engine_gradient_matches_reference(golden, name, prune, sparse_filter):
+    """Dense-gradient (data-parallel) variant of the fused backward: every
+    fixture's width and depth, pruned and full, each way of feeding the
+    first backward layer."""
+    f = golden(name)
+    m = lgcn_from(f, prune=prune)
+    m.engine.sparse_filter = sparse_filter
     t = torch.from_numpy(f["triples"]).cuda().int()
     w = m.all_embedding.weight
     out = m.engine.forward(w)
@@ -115,28 +121,48 @@ def test_engine_gradient_matches_reference(golden):
     assert int((m.engine.slot != -1).sum()) == 0  # seeds reset
 
 
-def test_engine_gradient_repeated_nodes_vs_oracle(golden):
-    """A batch where one item is the positive of 90 % of the triples and one
-    user appears 40 times (a Zipf-popular item: its seed run spans many
-    rounds of the seed accumulation's LPR-entry walk): the fused backward's
-    table gradient == the CPU oracle's autograd gradient."""
+@pytest.mark.parametrize("dim", [4, 16, 64, 256])
+def test_engine_gradient_repeated_nodes_vs_oracle(golden, dim):
+    """A batch where one item is the positive of 90 % of the triples, one
+    user appears 40 times and another LPR + 1 = dim / 4 + 1 times (a
+    Zipf-popular item: its seed run spans many rounds of the seed
+    accumulation's LPR-entry walk; LPR + 1 entries: one full round and one
+    entry of the next): the fused backward's table gradient == the CPU
+    oracle's autograd gradient.  dim 64 on the fixture graph, the other
+    widths on a synthetic one."""
+    from furusato_recommend_amd import LightGCN, SyntheticBipartite
     from oracle.lightgcn_oracle import OracleLightGCN
-    f = golden("lgcn_d64_L3.npz")
     B = 200
-    m = lgcn_from(f, batch=B)
-    n_users, m_items = int(f["n_users"]), int(f["m_items"])
+    if dim == 64:
+        f = golden("lgcn_d64_L3.npz")
+        m = lgcn_from(f, batch=B)
+        n_users, m_items = int(f["n_users"]), int(f["m_items"])
+        train, lr, decay = (f["train_user"], f["train_item"]), float(f["lr"]), float(f["decay"])
+        emb0 = torch.from_numpy(f["emb0"])
+    else:
+        ds = SyntheticBipartite(500, 120, 6000, seed=dim, test_frac=0.0)
+        torch.manual_seed(dim)
+        lr, decay = 1e-3, 1e-4
+        m = LightGCN({"recdim": dim, "layer": 3, "lr": lr, "decay": decay, "device": "cuda:0",
+                      "bpr_batch_size": B}, ds)
+        n_users, m_items = ds.n_users, ds.m_items
+        train = (ds.trainUser, ds.trainItem)
+        emb0 = m.all_embedding.weight.detach().cpu().clone()
+    lpr = dim // 4
     rng = np.random.default_rng(7)
     users = rng.integers(0, n_users, B)
+    users[users == 4] = 6
     users[:40] = 3
+    users[40:40 + lpr + 1] = 4
+    assert int((users == 4).sum()) == lpr + 1
     pos = np.where(rng.random(B) < 0.9, 5, rng.integers(0, m_items, B))
     neg = rng.integers(0, m_items, B)
-    o = OracleLightGCN(f["train_user"], f["train_item"], n_users, m_items, 64, 3,
-                       float(f["lr"]), float(f["decay"]), emb=torch.from_numpy(f["emb0"]))
+    o = OracleLightGCN(train[0], train[1], n_users, m_items, dim, 3, lr, decay, emb=emb0)
     ref = o.grad(torch.from_numpy(users), torch.from_numpy(pos), torch.from_numpy(neg))
     w = m.all_embedding.weight
     out = m.engine.forward(w)
     tc = [torch.from_numpy(a).cuda().int().contiguous() for a in (users, pos, neg)]
-    m.engine.bpr(out, w, *tc, float(f["decay"]))
+    m.engine.bpr(out, w, *tc, decay)
     g = torch.empty_like(w)
     m.engine.backward(w, grad_out=g)
     assert rel(g, ref) < TOL
@@ -415,24 +441,38 @@ def test_zipf_long_rows_match_unsplit(d):
     assert rel(outs[0], outs[1]) < 1e-5
 
 
-def test_seed_exchange_two_ranks_in_one_process(golden):
+@pytest.mark.parametrize("ways", [2, 3])
+@pytest.mark.parametrize("name", LGCN)
+def test_seed_exchange_two_ranks_in_one_process(golden, name, ways):
     """The DP sparse exchange (pack -> concatenate as an all-gather would ->
-    merge) for 2 simulated ranks == the reference gradient of the union."""
-    f = golden("lgcn_d64_L3.npz")
+    merge) for 2 or 3 simulated ranks == the reference gradient of the union
+    (3 ranks: the first 63 triples in equal parts, grad_scale = 1/3, against
+    the CPU oracle's gradient of those 63)."""
+    f = golden(name)
     m = lgcn_from(f)
     t = torch.from_numpy(f["triples"]).cuda().int()
+    if ways == 2:
+        parts, ref = (t[:32], t[32:]), f["grad"]
+    else:
+        from oracle.lightgcn_oracle import OracleLightGCN
+        parts = (t[:21], t[21:42], t[42:63])
+        o = OracleLightGCN(f["train_user"], f["train_item"], int(f["n_users"]),
+                           int(f["m_items"]), int(f["dim"]), int(f["n_layers"]), float(f["lr"]),
+                           float(f["decay"]), emb=torch.from_numpy(f["emb0"]))
+        t63 = torch.from_numpy(f["triples"][:63])
+        ref = o.grad(t63[:, 0], t63[:, 1], t63[:, 2])
     eng, w = m.engine, m.all_embedding.weight
     out = eng.forward(w)
-    parts = []
-    for half in (t[:32], t[32:]):
-        eng.bpr(out, w, half[:, 0].contiguous(), half[:, 1].contiguous(),
-                half[:, 2].contiguous(), float(f["decay"]), grad_scale=0.5)
-        parts.append([x.clone() for x in eng.export_seeds()])
+    gathered = []
+    for part in parts:
+        eng.bpr(out, w, part[:, 0].contiguous(), part[:, 1].contiguous(),
+                part[:, 2].contiguous(), float(f["decay"]), grad_scale=1.0 / ways)
+        gathered.append([x.clone() for x in eng.export_seeds()])
     assert int((eng.slot != -1).sum()) == 0
-    eng.import_seeds(*(torch.cat([parts[0][i], parts[1][i]]) for i in range(3)))
+    eng.import_seeds(*(torch.cat([g[i] for g in gathered]) for i in range(3)))
     g = torch.empty_like(w)
     eng.backward(w, grad_out=g)
-    assert rel(g, f["grad"]) < TOL
+    assert rel(g, ref) < TOL
     assert int((eng.slot != -1).sum()) == 0
 
 
