@@ -67,6 +67,11 @@ class Prop(Structure):
     ]
 
 
+class Drop(Structure):
+    """mirec_drop_t (the edge dropout of one mirec_propagate_drop launch)."""
+    _fields_ = [("keep_prob", c_float), ("transposed", c_int32), ("seed", c_uint64)]
+
+
 class Sweep(Structure):
     """mirec_sweep_t (column-sweep layout of the item rows)."""
     _fields_ = [
@@ -135,6 +140,10 @@ SIGNATURES = {
                                        c_int32, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
     "mirec_propagate_sweep_wave": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(SweepWave),
                                            POINTER(SweepWave), c_void_p]),
+    "mirec_drop_sizeof": (c_size_t, []),
+    "mirec_propagate_drop": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(Drop), c_void_p]),
+    "mirec_edge_keep_mask": (c_int, [c_void_p, c_void_p, c_int64, c_uint64, c_float, c_int32,
+                                     c_void_p]),
     "mirec_edge_dot": (c_int, [POINTER(CSR), c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "mirec_prescale": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "mirec_shard_pack": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_int64,
@@ -387,6 +396,8 @@ def _load():
         raise ImportError(f"struct layout mismatch: lib {[x.value for x in sizes]} vs {want}")
     if lib.mirec_row_grad_group_size() != ctypes.sizeof(RowGradGroup):
         raise ImportError("struct layout mismatch: mirec_row_grad_group_t")
+    if lib.mirec_drop_sizeof() != ctypes.sizeof(Drop):
+        raise ImportError("struct layout mismatch: mirec_drop_t")
     if lib.mirec_sweep_sizeof() != ctypes.sizeof(Sweep):
         raise ImportError("struct layout mismatch: mirec_sweep_t")
     if lib.mirec_sweep_wave_sizeof() != ctypes.sizeof(SweepWave):

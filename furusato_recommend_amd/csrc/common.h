@@ -134,6 +134,34 @@ __host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
   return x ^ (x >> 31);
 }
 
+// Edge dropout (prop.hip, mirec_prop_t drop_*; the formula is restated in
+// mirec.h): whether entry (src -> dst) of the adjacency survives under the
+// launch key.  A counter hash of the ORDERED pair, so (i, j) and (j, i) are
+// independent draws and every multi-edge of one (dst, src) shares its draw;
+// the transposed mask is the same function with the arguments swapped.
+// thresh_m1 = edge_drop_thresh(keep_prob) - 1 fits 32 bits for every
+// keep_prob in (0, 1]: keep_prob = 1 gives 0xffffffff, which keeps all.
+__host__ __device__ __forceinline__ uint64_t edge_drop_key(uint64_t seed) {
+  return mix64(seed ^ 0xD6E8FEB86659FD93ull);
+}
+
+__host__ __device__ __forceinline__ bool edge_keep(uint64_t key, uint32_t dst, uint32_t src,
+                                                   uint32_t thresh_m1) {
+  const uint64_t h = mix64(key ^ (((uint64_t)dst << 32) | (uint64_t)src));
+  return (uint32_t)(h >> 32) <= thresh_m1;
+}
+
+// floor(keep_prob * 2^32) clamped to [1, 2^32], minus one; false unless
+// 0 < keep_prob <= 1 (NaN included).
+static inline bool edge_drop_thresh(float keep_prob, uint32_t *thresh_m1) {
+  if (!(keep_prob > 0.f && keep_prob <= 1.f)) return false;
+  uint64_t t = (uint64_t)((double)keep_prob * 4294967296.0);
+  if (t < 1) t = 1;
+  if (t > 4294967296ull) t = 4294967296ull;
+  *thresh_m1 = (uint32_t)(t - 1);
+  return true;
+}
+
 __device__ __forceinline__ bool keep(uint64_t key, uint64_t idx, uint32_t thresh) {
   const uint64_t h = mix64(key + (idx >> 2));
   return (uint32_t)((h >> (16 * (idx & 3))) & 0xffffu) >= thresh;

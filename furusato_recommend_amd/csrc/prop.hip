@@ -43,6 +43,15 @@
 // own vectors (D^-(1-r) A D^-r and its transpose, model/radj.py:28-44).  The
 // other instantiations are the earlier ones, instruction for instruction.
 //
+// Edge dropout (mirec_propagate_drop, the reference's __dropout_x,
+// model/MF.py:158-176): the kDropout instantiations keep entry (j -> i) iff
+// edge_keep(key, i, j) (common.h; a hash of the ordered pair, multi-edges
+// share the draw), decided by the lane that has just loaded the column; the
+// dropped ones leave through the in_mask compaction, which a launch without
+// another filter runs for them alone, so their rows are never gathered.  The
+// transposed mask (backward) swaps the two hash arguments on the same CSR.
+// The other instantiations are the earlier ones, instruction for instruction.
+//
 // Epilogue (per row, LPR lanes): z = dinv_i * sum + seed[slot_i];
 // xs_out = dinv_i * z (next layer's pre-scaled input);
 // o = (z + addend)/divisor + seed2[slot_i]; out = o or Adam(param; grad=o).
@@ -82,10 +91,26 @@ struct PropK {
   int32_t narrow_max;        // rows up to this degree are gathered group-per-row
   const int32_t *wide_list;  // rows gathered by a whole workgroup each (list mode)
   const int32_t *wide_count;
-  const float *val;          // [nnz] per-entry weight (WEIGHTED instantiations only)
+  // A DROPOUT launch (edge dropout, common.h edge_keep) has neither values nor
+  // scales of its own (refused by the host), so its four scalars live in the
+  // storage of those three pointers: PropK, and with it the argument block of
+  // every other instantiation, keeps its size and its offsets.
+  union {
+    const float *val;        // [nnz] per-entry weight (WEIGHTED instantiations only)
+    uint64_t drop_key;       // DROPOUT: edge_drop_key(seed)
+  };
   // SCALED instantiations only (there `dinv` above is the row sum's scale):
-  const float *scale_src;    // [n_rows] scale of a gathered neighbour (RAW, SPARSE)
-  const float *scale_next;   // [n_rows] scale of the row written to xs_out
+  union {
+    const float *scale_src;  // [n_rows] scale of a gathered neighbour (RAW, SPARSE)
+    struct {
+      uint32_t drop_thresh_m1;  // DROPOUT: edge_drop_thresh(keep_prob) - 1
+      int32_t drop_transposed;  // DROPOUT: entry (j -> i) is masked by keep(j, i)
+    };
+  };
+  union {
+    const float *scale_next;  // [n_rows] scale of the row written to xs_out
+    float drop_scale;         // DROPOUT: 1 / keep_prob, applied once to a gathered sum
+  };
 };
 
 // prop_kernel's MODE argument with this bit set is the edge-weighted walk
@@ -94,6 +119,9 @@ constexpr int kWeighted = 4;
 // ... and with this bit the three scales come from their own vectors
 // (never together with kWeighted: refused by the host).
 constexpr int kScaled = 8;
+// ... and with this bit every entry is kept or dropped by edge_keep (edge
+// dropout; never together with kWeighted or kScaled: refused by the host).
+constexpr int kDropout = 16;
 
 __device__ __forceinline__ bool bit_set(const uint8_t *bm, int64_t i) { return bm[i] != 0; }
 
@@ -117,9 +145,16 @@ __device__ __forceinline__ bool bit_set(const uint8_t *bm, int64_t i) { return b
 // weight becomes val (PRESCALED, which then takes the fma form) or
 // val * dinv_j (RAW, SPARSE).  Same order of terms as the unweighted sum.
 // SCALED: the neighbour's scale is scale_src_j instead of dinv_j.
+// DROPOUT: the lane that holds a column evaluates edge_keep for (row, column)
+// ((column, row) in a transposed launch); the result joins the filter of the
+// compaction, or is the whole filter of a launch without one, so a dropped
+// neighbour's row is never read; the sum of the kept ones, in CSR order, is
+// scaled by 1 / keep_prob once.  `row` is the destination row of [beg, end)
+// (NARROW: of this lane's group); the other instantiations ignore it.
 template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED, bool NARROW,
-          bool SCALED = false>
-__device__ __forceinline__ float4 gather(const PropK &a, int64_t beg, int64_t end, int lane) {
+          bool SCALED = false, bool DROPOUT = false>
+__device__ __forceinline__ float4 gather(const PropK &a, int64_t beg, int64_t end, int lane,
+                                         int32_t row = 0) {
   constexpr int LPR = D / 4;
   constexpr int G = 64 / LPR;
   constexpr int W = NARROW ? LPR : 64;  // entries per chunk = lanes sharing it
@@ -141,8 +176,14 @@ __device__ __forceinline__ float4 gather(const PropK &a, int64_t beg, int64_t en
     // of the hits only: fewer slot reads when many neighbours are seeded)
     const bool slot_filter = MODE == MIREC_IN_SPARSE && a.in_mask == nullptr;
     int myr = slot_filter ? (me < cnt ? a.slot[myc] : -1) : myc;
-    if (MASKED) {
-      const bool ok = me < cnt && (slot_filter ? myr >= 0 : bit_set(a.in_mask, myc));
+    if (MASKED || DROPOUT) {
+      bool ok = me < cnt;
+      if (MASKED) ok = me < cnt && (slot_filter ? myr >= 0 : bit_set(a.in_mask, myc));
+      if constexpr (DROPOUT) {
+        const uint32_t r = (uint32_t)row, c = (uint32_t)myc;
+        ok = ok && edge_keep(a.drop_key, a.drop_transposed ? c : r, a.drop_transposed ? r : c,
+                             a.drop_thresh_m1);
+      }
       const unsigned long long bal = __ballot(ok);
       const unsigned long long m = (W == 64) ? bal : ((bal >> l0) & ((1ull << W) - 1ull));
       const int nv = __popcll(m);
@@ -191,6 +232,7 @@ __device__ __forceinline__ float4 gather(const PropK &a, int64_t beg, int64_t en
       }
     }
   }
+  if constexpr (DROPOUT) acc = f4_scale(a.drop_scale, acc);
   return acc;
 }
 
@@ -255,7 +297,8 @@ constexpr int kWavesPerBlock = 4;
 // short list does not pay for its host-side capacity in empty waves.
 // MASKED = in_mask filter on neighbours, ROWMASK = row_mask filter on rows
 // (separate instantiations so profiles tell full and pruned launches apart).
-template <int D, int UNROLL, int MODE, bool MASKED, bool ROWMASK, bool WEIGHTED, bool SCALED>
+template <int D, int UNROLL, int MODE, bool MASKED, bool ROWMASK, bool WEIGHTED, bool SCALED,
+          bool DROPOUT>
 __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nrows,
                                           int64_t row_waves) {
   constexpr int LPR = D / 4;
@@ -281,7 +324,8 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
     }
     const int64_t deg = have ? end - beg : 0;
     if (G > 1 && __ballot(deg > a.narrow_max) == 0ull) {
-      float4 s = gather<D, NARROW_UNROLL, MODE, MASKED, WEIGHTED, true, SCALED>(a, beg, end, lane);
+      float4 s = gather<D, NARROW_UNROLL, MODE, MASKED, WEIGHTED, true, SCALED, DROPOUT>(
+          a, beg, end, lane, row);
       if (have) row_epilogue<D, SCALED>(a, row, s, sub);
       return;
     }
@@ -292,7 +336,8 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
       const int32_t r = __shfl(row, src);
       const int64_t rb = __shfl((long long)beg, src);
       const int64_t re = __shfl((long long)end, src);
-      float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED>(a, rb, re, lane);
+      float4 s =
+          gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED, DROPOUT>(a, rb, re, lane, r);
       s = combine_groups<D>(s);
       if (lane < LPR) row_epilogue<D, SCALED>(a, r, s, sub);
     }
@@ -303,7 +348,9 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
     if (ROWMASK && !bit_set(a.row_mask, row)) return;
     const int64_t beg = a.seg_beg[sg];
     const int64_t end = min(beg + (int64_t)a.split, a.rowptr[row + 1]);
-    float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED>(a, beg, end, lane);
+    float4 s =
+        gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED, DROPOUT>(a, beg, end, lane,
+                                                                          (int32_t)row);
     s = combine_groups<D>(s);
     if (lane < LPR) st4(a.partial + sg * D + sub * 4, s);
   }
@@ -313,7 +360,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
 // quarter of the row's entries, the four wave sums are added in wave order
 // through LDS (deterministic), wave 0 runs the epilogue.  Block-uniform
 // control flow (contains barriers).
-template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED, bool SCALED>
+template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED, bool SCALED, bool DROPOUT>
 __device__ __forceinline__ void block_row(const PropK &a, int32_t row) {
   constexpr int LPR = D / 4;
   __shared__ float4 red[kWavesPerBlock - 1][LPR];
@@ -324,7 +371,8 @@ __device__ __forceinline__ void block_row(const PropK &a, int32_t row) {
   if (a.split > 0 && end - beg > a.split) return;  // segments handle it (uniform)
   const int64_t q = (end - beg + kWavesPerBlock - 1) / kWavesPerBlock;
   const int64_t wb = min(beg + wid * q, end), we = min(wb + q, end);
-  float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED>(a, wb, we, lane);
+  float4 s =
+      gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED, DROPOUT>(a, wb, we, lane, row);
   s = combine_groups<D>(s);
   if (wid > 0 && lane < LPR) red[wid - 1][sub] = s;
   __syncthreads();
@@ -337,13 +385,14 @@ __device__ __forceinline__ void block_row(const PropK &a, int32_t row) {
 }
 
 // One row gathered by one wave.
-template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED, bool SCALED>
+template <int D, int UNROLL, int MODE, bool MASKED, bool WEIGHTED, bool SCALED, bool DROPOUT>
 __device__ __forceinline__ void wave_row(const PropK &a, int32_t row) {
   constexpr int LPR = D / 4;
   const int lane = threadIdx.x & 63;
   const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
   if (a.split > 0 && end - beg > a.split) return;  // segments handle it
-  float4 s = gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED>(a, beg, end, lane);
+  float4 s =
+      gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED, DROPOUT>(a, beg, end, lane, row);
   s = combine_groups<D>(s);
   if (lane < LPR) row_epilogue<D, SCALED>(a, row, s, lane % LPR);
 }
@@ -357,18 +406,20 @@ constexpr int64_t kListBlocks = 8192;
 // Occupancy floor (waves per SIMD): keeps the register allocator at <= 72
 // VGPRs so 7-8 waves per SIMD keep enough gathers in flight.
 // MODE_W = in_mode, + kWeighted for an edge-weighted launch (csr->val), or
-// + kScaled for a launch with scale vectors of its own.
+// + kScaled for a launch with scale vectors of its own, or + kDropout for an
+// edge-dropout launch.
 template <int D, int UNROLL, int MODE_W, bool MASKED, bool ROWMASK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8)))
 MIREC_NO_PK_F32 void prop_kernel(PropK a) {
   constexpr int MODE = MODE_W & 3;
   constexpr bool WEIGHTED = (MODE_W & kWeighted) != 0;
   constexpr bool SCALED = (MODE_W & kScaled) != 0;
+  constexpr bool DROPOUT = (MODE_W & kDropout) != 0;
   constexpr int G = 64 / (D / 4);
   // wave index made provably uniform (SGPR): loop control stays scalar
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (!ROWMASK || a.row_list == nullptr) {
-    prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED, SCALED>(
+    prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED, SCALED, DROPOUT>(
         a, (int64_t)blockIdx.x * kWavesPerBlock + wid, a.n_rows, a.row_waves);
     return;
   }
@@ -389,15 +440,17 @@ MIREC_NO_PK_F32 void prop_kernel(PropK a) {
   for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
     if (b < wide_blocks) {
       if constexpr (WPB == 1) {
-        block_row<D, UNROLL, MODE, MASKED, WEIGHTED, SCALED>(a, a.wide_list[b]);
+        block_row<D, UNROLL, MODE, MASKED, WEIGHTED, SCALED, DROPOUT>(a, a.wide_list[b]);
       } else {
         const int64_t i = b * WPB + wid;
-        if (i < n_wide) wave_row<D, UNROLL, MODE, MASKED, WEIGHTED, SCALED>(a, a.wide_list[i]);
+        if (i < n_wide)
+          wave_row<D, UNROLL, MODE, MASKED, WEIGHTED, SCALED, DROPOUT>(a, a.wide_list[i]);
       }
     } else {
       const int64_t w = (b - wide_blocks) * kWavesPerBlock + wid;
       if (w < waves)
-        prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED, SCALED>(a, w, nrows, row_waves);
+        prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED, SCALED, DROPOUT>(a, w, nrows,
+                                                                               row_waves);
     }
   }
 }
@@ -734,16 +787,20 @@ using PropFn = void (*)(PropK);
 // unweighted (it reads no neighbours).  The cases stand in the order the
 // kernels have in the code object, which follows their first use here.
 // The kScaled cases come after all the earlier ones, so those keep their
-// places; scaled and weighted never meet (refused in propagate()).
+// places; scaled and weighted never meet (refused in propagate()).  The
+// kDropout cases follow them in turn (dropout meets neither; a NONE launch
+// gathers nothing, so it has no dropout form).
 template <int D, int UNROLL>
-static PropFn prop_kernel_for(int mode, bool masked, bool rowmask, bool weighted, bool scaled) {
+static PropFn prop_kernel_for(int mode, bool masked, bool rowmask, bool weighted, bool scaled,
+                              bool dropout) {
   if (mode == MIREC_IN_SPARSE) masked = true;
-  if (mode == MIREC_IN_NONE) weighted = false;
+  if (mode == MIREC_IN_NONE) weighted = dropout = false;
 #define MIREC_PROP_CASE(MODE_W, MASKED)                               \
   case (MODE_W) * 2 + (MASKED):                                       \
     return rowmask ? prop_kernel<D, UNROLL, (MODE_W), MASKED, true>   \
                    : prop_kernel<D, UNROLL, (MODE_W), MASKED, false>;
-  switch ((mode | (weighted ? kWeighted : 0) | (scaled ? kScaled : 0)) * 2 + masked) {
+  switch ((mode | (weighted ? kWeighted : 0) | (scaled ? kScaled : 0) |
+           (dropout ? kDropout : 0)) * 2 + masked) {
     MIREC_PROP_CASE(MIREC_IN_PRESCALED | kWeighted, false)
     MIREC_PROP_CASE(MIREC_IN_PRESCALED, false)
     MIREC_PROP_CASE(MIREC_IN_PRESCALED | kWeighted, true)
@@ -760,6 +817,11 @@ static PropFn prop_kernel_for(int mode, bool masked, bool rowmask, bool weighted
     MIREC_PROP_CASE(MIREC_IN_RAW | kScaled, true)
     MIREC_PROP_CASE(MIREC_IN_SPARSE | kScaled, true)
     MIREC_PROP_CASE(MIREC_IN_NONE | kScaled, false)
+    MIREC_PROP_CASE(MIREC_IN_PRESCALED | kDropout, false)
+    MIREC_PROP_CASE(MIREC_IN_PRESCALED | kDropout, true)
+    MIREC_PROP_CASE(MIREC_IN_RAW | kDropout, false)
+    MIREC_PROP_CASE(MIREC_IN_RAW | kDropout, true)
+    MIREC_PROP_CASE(MIREC_IN_SPARSE | kDropout, true)
     default:  // in_mask is refused with NONE (mirec_propagate_sweep)
     MIREC_PROP_CASE(MIREC_IN_NONE, false)
   }
@@ -768,11 +830,12 @@ static PropFn prop_kernel_for(int mode, bool masked, bool rowmask, bool weighted
 
 template <int D, int UNROLL>
 static int launch_prop(const mirec_csr_t *c, PropK k, int64_t list_cap, int mode,
-                       hipStream_t st) {
+                       hipStream_t st, bool dropout = false) {
   constexpr int G = 64 / (D / 4);
   const int64_t rows = k.row_list != nullptr ? list_cap : c->n_rows;
   k.row_waves = (rows + G - 1) / G;
   const int64_t work = k.row_waves + c->n_seg;
+  const bool scaled = !dropout && k.scale_next != nullptr;  // (shared storage, PropK)
   int64_t blocks = (work + kWavesPerBlock - 1) / kWavesPerBlock;
   if (k.row_list != nullptr) {
     if (k.wide_list != nullptr) blocks += list_cap;
@@ -781,12 +844,12 @@ static int launch_prop(const mirec_csr_t *c, PropK k, int64_t list_cap, int mode
   if (blocks > 0) {
     const PropFn kernel =
         prop_kernel_for<D, UNROLL>(mode, k.in_mask != nullptr, k.row_mask != nullptr,
-                                   k.val != nullptr, k.scale_next != nullptr);
+                                   !dropout && k.val != nullptr, scaled, dropout);
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, k);
     MIREC_LAUNCH_CHECK();
   }
   if (c->n_long > 0) {
-    const auto fin = k.scale_next != nullptr ? prop_finalize<D, true> : prop_finalize<D, false>;
+    const auto fin = scaled ? prop_finalize<D, true> : prop_finalize<D, false>;
     hipLaunchKernelGGL(fin, dim3((unsigned)c->n_long), dim3(256), 0, st, k, c->long_rows,
                        c->long_segptr, c->n_long);
     MIREC_LAUNCH_CHECK();
@@ -994,7 +1057,7 @@ namespace mirec {
 // form) and `wi` (wave form, `wu` optional beside it) is given.
 static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sweep_t *sw,
                      const mirec_sweep_wave_t *wi, const mirec_sweep_wave_t *wu,
-                     mirec_stream_t stream) {
+                     mirec_stream_t stream, const mirec_drop_t *drop = nullptr) {
   MIREC_CHECK_ARG(c != nullptr && p != nullptr);
   MIREC_CHECK_ARG(c->rowptr != nullptr && c->dinv != nullptr && c->n_rows >= 0);
   MIREC_CHECK_ARG(c->nnz == 0 || c->col != nullptr);
@@ -1059,6 +1122,21 @@ static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sw
     k.dinv = p->scale_dst != nullptr ? p->scale_dst : c->dinv;
     k.scale_next = p->scale_next != nullptr ? p->scale_next : c->dinv;
   }
+  // Edge dropout (mirec_propagate_drop, keep_prob != 0) runs the kDropout
+  // instantiations: no edge weights, no scales of its own, keep_prob in (0, 1]
+  // (a NaN fails too); it comes without sweep layouts (the sweep kernels have
+  // no mask), so it runs the row kernel below.
+  const bool dropout = drop != nullptr && drop->keep_prob != 0.f;
+  if (dropout) {
+    uint32_t thresh_m1 = 0;
+    MIREC_CHECK_ARG(edge_drop_thresh(drop->keep_prob, &thresh_m1));
+    MIREC_CHECK_ARG(c->val == nullptr && !scaled);
+    k.drop_key = edge_drop_key(drop->seed);  // (the storage of val and the scales)
+    k.drop_thresh_m1 = thresh_m1;
+    k.drop_transposed = drop->transposed != 0;
+    k.scale_next = nullptr;  // (all 8 bytes of the storage drop_scale shares)
+    k.drop_scale = 1.f / drop->keep_prob;
+  }
   const int64_t cap = p->row_list_cap;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (sweep_qualifies(c, p, sw)) return launch_sweep<64, 4>(c, k, sw, st);
@@ -1070,13 +1148,13 @@ static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sw
     return launch_head<64, 4>(c, k, wi->row0, st);
   }
   switch (p->dim) {
-    case 4: return launch_prop<4, 1>(c, k, cap, p->in_mode, st);
-    case 8: return launch_prop<8, 1>(c, k, cap, p->in_mode, st);
-    case 16: return launch_prop<16, 1>(c, k, cap, p->in_mode, st);
-    case 32: return launch_prop<32, 2>(c, k, cap, p->in_mode, st);
-    case 64: return launch_prop<64, 4>(c, k, cap, p->in_mode, st);
-    case 128: return launch_prop<128, 4>(c, k, cap, p->in_mode, st);
-    case 256: return launch_prop<256, 8>(c, k, cap, p->in_mode, st);
+    case 4: return launch_prop<4, 1>(c, k, cap, p->in_mode, st, dropout);
+    case 8: return launch_prop<8, 1>(c, k, cap, p->in_mode, st, dropout);
+    case 16: return launch_prop<16, 1>(c, k, cap, p->in_mode, st, dropout);
+    case 32: return launch_prop<32, 2>(c, k, cap, p->in_mode, st, dropout);
+    case 64: return launch_prop<64, 4>(c, k, cap, p->in_mode, st, dropout);
+    case 128: return launch_prop<128, 4>(c, k, cap, p->in_mode, st, dropout);
+    case 256: return launch_prop<256, 8>(c, k, cap, p->in_mode, st, dropout);
   }
   return MIREC_ERR_DIM;
 }
@@ -1098,6 +1176,32 @@ extern "C" int mirec_propagate_sweep_wave(const mirec_csr_t *c, const mirec_prop
                                           const mirec_sweep_wave_t *users,
                                           mirec_stream_t stream) {
   return mirec::propagate(c, p, nullptr, items, users, stream);
+}
+
+extern "C" size_t mirec_drop_sizeof(void) { return sizeof(mirec_drop_t); }
+
+extern "C" int mirec_propagate_drop(const mirec_csr_t *c, const mirec_prop_t *p,
+                                    const mirec_drop_t *drop, mirec_stream_t stream) {
+  return mirec::propagate(c, p, nullptr, nullptr, nullptr, stream, drop);
+}
+
+extern "C" int mirec_edge_keep_mask(const int64_t *rowptr, const int32_t *col, int64_t n_rows,
+                                    uint64_t seed, float keep_prob, int32_t transposed,
+                                    uint8_t *keep) {
+  using namespace mirec;
+  MIREC_CHECK_ARG(rowptr != nullptr && n_rows >= 0);
+  uint32_t thresh_m1 = 0;
+  MIREC_CHECK_ARG(edge_drop_thresh(keep_prob, &thresh_m1));
+  if (n_rows == 0 || rowptr[n_rows] == rowptr[0]) return MIREC_OK;
+  MIREC_CHECK_ARG(col != nullptr && keep != nullptr);
+  const uint64_t key = edge_drop_key(seed);
+  for (int64_t i = 0; i < n_rows; ++i) {
+    for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+      const uint32_t r = (uint32_t)i, c = (uint32_t)col[e];
+      keep[e] = edge_keep(key, transposed ? c : r, transposed ? r : c, thresh_m1) ? 1 : 0;
+    }
+  }
+  return MIREC_OK;
 }
 
 extern "C" int mirec_edge_dot(const mirec_csr_t *c, const float *a, const float *b, int32_t dim,

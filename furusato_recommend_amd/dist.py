@@ -97,6 +97,11 @@ class DataParallel:
                  chunks: int | None = None):
         if mode not in self.MODES:
             raise ValueError(mode)
+        if getattr(engine, "edge_dropout", None) is not None:
+            # the ranks' steps would have to agree on one mask per step through
+            # the seed exchange and the sharded update; not verified yet
+            raise NotImplementedError("data-parallel training with edge dropout "
+                                      "(config['dropout']) is not implemented")
         self.requested = mode
         self.mode = "sparse" if mode == "auto" else mode
         self.engine = engine

@@ -343,6 +343,41 @@ class PropagationEngine:
         # pruned forward or any update): repeated getUsersRating calls of one
         # evaluation reuse it instead of re-propagating
         self._acc_full = None
+        # Edge dropout.  ``edge_dropout`` is the owner's
+        # setting (a keep_prob while its model trains with dropout, else
+        # None; the data-parallel wrappers refuse it); ``_drop`` is the state
+        # of the step being issued: (keep_prob, seed) or None = the full graph.
+        self.edge_dropout = None
+        self._drop = None
+
+    # -------------------------------------------------------- edge dropout
+    @staticmethod
+    def dropout_seed(seed: int, step: int) -> int:
+        """The mask seed of training step ``step`` (0, 1, ...) of a run seeded
+        with ``seed``: (seed mod 2^32) * 2^32 + (step mod 2^32).  The same on
+        every rank; mirec_edge_keep_mask with it restates the step's mask."""
+        return ((int(seed) & 0xFFFFFFFF) << 32) | (int(step) & 0xFFFFFFFF)
+
+    def set_dropout(self, keep_prob: float | None, seed: int = 0):
+        """Every propagation launch from now on runs on the graph whose entry
+        (j → i) is kept iff mirec_edge_keep(seed, i, j), scaled by
+        1 / keep_prob ("bwd" launches: the transposed mask); None restores
+        the full graph.  One state serves the forward and every backward
+        launch of a step, so the backward differentiates the forward's
+        matrix."""
+        if keep_prob is None:
+            self._drop = None
+            return
+        kp = float(keep_prob)
+        if not (0.0 < kp <= 1.0):
+            raise ValueError(f"edge dropout: keep_prob must lie in (0, 1], got {keep_prob!r}")
+        if self.g.val is not None or self.g.scale_src is not None:
+            raise ValueError("edge dropout is not combined with edge weights or an "
+                             "r-adjusted normalisation")
+        self._drop = (kp, int(seed) & (2 ** 64 - 1))
+        # neither cache may carry over between the full and a dropped graph
+        # (x0s = dinv ⊙ E is the same for both and stays)
+        self._acc_full = None
 
     # ------------------------------------------------------------ internals
     def _ensure_ws(self, batch: int):
@@ -408,7 +443,15 @@ class PropagationEngine:
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record()
         on = self.use_sweep and g is self.g
-        if on and self._sweep_form == "wave":
+        if self._drop is not None:
+            # a dropped launch has an entry point of its own (and no swept form)
+            if direction not in ("fwd", "bwd", "bwd_last"):
+                raise ValueError(f"direction: 'fwd', 'bwd' or 'bwd_last', got {direction!r}")
+            drop = _lib.Drop(keep_prob=self._drop[0], transposed=int(direction != "fwd"),
+                             seed=self._drop[1])
+            check(lib.mirec_propagate_drop(g.csr_ptr(), ctypes.byref(p), ctypes.byref(drop),
+                                           _lib.stream_handle()), "propagate_drop")
+        elif on and self._sweep_form == "wave":
             wi, wu = self.sweep_wave, self.sweep_wave_users if self._sweep_users else None
             check(lib.mirec_propagate_sweep_wave(g.csr_ptr(), ctypes.byref(p),
                                                  wi.ptr() if wi is not None else None,
@@ -656,6 +699,8 @@ class PropagationEngine:
         for l in range(1, L + 1):
             last = l == L
             rows = {}
+            # (under edge dropout too: S ∪ N(S) of the full graph is a superset
+            # of the dropped graph's frontier, the pruned rows stay exact)
             if pruned and l == L:      # S: the deduplicated batch-node list
                 rows = self._self_rows()
             elif pruned and l == L - 1:  # F1 = S ∪ N(S)
@@ -670,7 +715,9 @@ class PropagationEngine:
                        out=self.acc,
                        xs_out=None if last else self.xs[(l - 1) % 2],
                        **rows)
-        if not pruned:
+        # a dropped forward is never the evaluation's propagation: it leaves
+        # no full-propagation token behind (forward_cached re-propagates)
+        if not pruned and self._drop is None:
             self._acc_full = self._token(emb)
         return self.acc
 
@@ -850,11 +897,27 @@ class PropagationEngine:
         return self.forward(emb, pruned=self.prune)
 
     def train_step(self, emb: torch.Tensor, adam: AdamState, users, pos, neg, decay: float,
-                   loss_accum: torch.Tensor | None = None) -> torch.Tensor:
-        """stageOne: forward, BPR, backward, fused Adam.  Returns loss (device)."""
-        out = self.forward_for_batch(emb, users, pos, neg)
-        loss = self.bpr(out, emb, users, pos, neg, decay, loss_accum)
-        self.backward(emb, adam=adam)
+                   loss_accum: torch.Tensor | None = None, dropout=None) -> torch.Tensor:
+        """stageOne: forward, BPR, backward, fused Adam.  Returns loss (device).
+
+        ``dropout`` = (keep_prob, seed): the step runs on the edge-dropped
+        graph of that seed (the reference's __dropout_x, model/MF.py:158-176),
+        one mask for the forward and every backward launch; the caller passes
+        a new seed per step (dropout_seed).  Frontier pruning stays on: the
+        structural frontier S ∪ N(S) contains the dropped graph's, so the
+        rows and neighbours it skips are exact zeros under any mask too."""
+        if dropout is None:
+            out = self.forward_for_batch(emb, users, pos, neg)
+            loss = self.bpr(out, emb, users, pos, neg, decay, loss_accum)
+            self.backward(emb, adam=adam)
+            return loss
+        self.set_dropout(*dropout)
+        try:
+            out = self.forward_for_batch(emb, users, pos, neg)
+            loss = self.bpr(out, emb, users, pos, neg, decay, loss_accum)
+            self.backward(emb, adam=adam)
+        finally:
+            self.set_dropout(None)
         return loss
 
 
@@ -874,10 +937,14 @@ def edge_dot(graph: Graph, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor):
                              _lib.stream_handle()), "edge_dot")
 
 
-def propagate(graph: Graph, x: torch.Tensor, out: torch.Tensor):
+def propagate(graph: Graph, x: torch.Tensor, out: torch.Tensor, dropout=None,
+              transposed: bool = False):
     """out = Â x on ``graph`` (one LGConv call; x, out: contiguous fp32
     [n_nodes, D] device tensors, D in SUPPORTED_DIMS; edge-weighted when the
-    graph carries values, r-adjusted when it carries scales)."""
+    graph carries values, r-adjusted when it carries scales).  ``dropout`` =
+    (keep_prob, seed): on the edge-dropped matrix (entry (j → i) kept iff
+    mirec_edge_keep(seed, i, j), kept entries / keep_prob); ``transposed``
+    applies the mask of the transposed matrix, keep(seed, j, i)."""
     n, D = x.shape
     if D not in _lib.SUPPORTED_DIMS or n != graph.n_nodes or out.shape != x.shape:
         raise ValueError(f"propagate: x {tuple(x.shape)}, out {tuple(out.shape)}, "
@@ -895,6 +962,15 @@ def propagate(graph: Graph, x: torch.Tensor, out: torch.Tensor):
     if graph.scale_src is not None:
         p.scale_src = graph.scale_src.data_ptr()
         p.scale_dst = graph.scale_dst.data_ptr()
+    if dropout is not None:
+        kp, seed = dropout
+        if not (0.0 < float(kp) <= 1.0):
+            raise ValueError(f"edge dropout: keep_prob must lie in (0, 1], got {kp!r}")
+        drop = _lib.Drop(keep_prob=float(kp), transposed=int(bool(transposed)),
+                         seed=int(seed) & (2 ** 64 - 1))
+        check(lib.mirec_propagate_drop(graph.csr_ptr(), ctypes.byref(p), ctypes.byref(drop),
+                                       _lib.stream_handle()), "propagate_drop")
+        return
     check(lib.mirec_propagate(graph.csr_ptr(), ctypes.byref(p), _lib.stream_handle()),
           "propagate")
 

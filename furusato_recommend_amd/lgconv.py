@@ -45,12 +45,13 @@ def _width(d: int) -> int:
     return 256
 
 
-def _spmm(graph: Graph, x: torch.Tensor) -> torch.Tensor:
+def _spmm(graph: Graph, x: torch.Tensor, **drop) -> torch.Tensor:
+    """Â x for any width; ``drop`` = engine.propagate's dropout / transposed."""
     n, d = x.shape
     if d in _lib.SUPPORTED_DIMS:
         xc = x.contiguous()
         y = torch.empty_like(xc)
-        propagate(graph, xc, y)
+        propagate(graph, xc, y, **drop)
         return y
     outs = []
     for c0 in range(0, d, 256):
@@ -58,7 +59,7 @@ def _spmm(graph: Graph, x: torch.Tensor) -> torch.Tensor:
         w = _width(xb.shape[1])
         xp = F.pad(xb, (0, w - xb.shape[1])).contiguous()
         yp = torch.empty_like(xp)
-        propagate(graph, xp, yp)
+        propagate(graph, xp, yp, **drop)
         outs.append(yp[:, :xb.shape[1]])
     return torch.cat(outs, 1) if len(outs) > 1 else outs[0].contiguous()
 

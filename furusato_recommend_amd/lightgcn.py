@@ -31,9 +31,16 @@ class _Propagate(torch.autograd.Function):
     """out = (Σ_{l=0..L} Â^l E)/(L+1) with a HIP backward (Horner, dense seed)."""
 
     @staticmethod
-    def forward(ctx, emb, engine: PropagationEngine):
+    def forward(ctx, emb, engine: PropagationEngine, dropout=None):
         ctx.engine = engine
-        return engine.forward(emb.contiguous()).clone()
+        ctx.dropout = dropout  # (keep_prob, seed) of THIS forward, or None
+        if dropout is None:
+            return engine.forward(emb.contiguous()).clone()
+        engine.set_dropout(*dropout)
+        try:
+            return engine.forward(emb.contiguous()).clone()
+        finally:
+            engine.set_dropout(None)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -41,13 +48,20 @@ class _Propagate(torch.autograd.Function):
         L = eng.L
         d = (grad_out.contiguous() / float(L + 1))
         if L == 0:
-            return d, None
+            return d, None, None
         g = d
-        for _ in range(L):
-            nxt = torch.empty_like(d)
-            eng.propagate_accumulate(g, d, nxt, transposed=True)
-            g = nxt
-        return g, None
+        # the transposed mask of this node's own forward, whatever the engine
+        # has run since
+        if ctx.dropout is not None:
+            eng.set_dropout(*ctx.dropout)
+        try:
+            for _ in range(L):
+                nxt = torch.empty_like(d)
+                eng.propagate_accumulate(g, d, nxt, transposed=True)
+                g = nxt
+        finally:
+            eng.set_dropout(None)
+        return g, None, None
 
 
 def _config_get(config, *keys, default=None):
@@ -61,6 +75,8 @@ class LightGCN(nn.Module):
     """model/lgcn.py:44-151 on MI355X.  ``config["r"]`` is ignored here (the
     reference's 'lgn' ignores it too): the normalisation is deg^-1/2 on both
     sides; ``rAdjGCN`` is the model that reads it."""
+
+    edge_dropout_supported = True  # config["dropout"]; rAdjGCN refuses it
 
     def _graph_r(self, config) -> float:
         """The r of the graph's normalisation 1 / (deg_j^r · deg_i^(1−r))."""
@@ -87,6 +103,25 @@ class LightGCN(nn.Module):
         if weight is not None and len(weight) != len(dataset.trainUser):
             raise ValueError(f"config['edge_weight']: {len(weight)} weights for "
                              f"{len(dataset.trainUser)} training interactions")
+        # config["dropout"] / config["keep_prob"] (parse.py:16-18, world.py:
+        # 38-39; the flat key "keepprob" is accepted too): the original
+        # LightGCN's edge dropout (model/MF.py:158-176, 187-194).  While the
+        # module is in training mode every step (stageOne, OneEpoch, forward /
+        # bpr_loss) runs on a graph whose entries are kept with probability
+        # keep_prob and divided by it, one mask per step shared by all layers
+        # and by the backward; eval() restores the full graph.
+        self.dropout = bool(int(_config_get(config, "dropout", default=0) or 0))
+        self.keep_prob = float(_config_get(config, "keep_prob", "keepprob", default=0.6))
+        self._drop_step = 0  # steps taken under dropout: the mask sequence's position
+        if self.dropout:
+            if not (0.0 < self.keep_prob <= 1.0):
+                raise ValueError(f"config['keep_prob'] must lie in (0, 1], got {self.keep_prob!r}")
+            if weight is not None:
+                raise ValueError("config['dropout'] with config['edge_weight']: edge dropout "
+                                 "and edge weights are not combined")
+            if not self.edge_dropout_supported:
+                raise ValueError(f"config['dropout'] with {type(self).__name__}: edge dropout "
+                                 "and the r-adjusted normalisation's scales are not combined")
         self.graph = Graph.from_interactions(dataset.trainUser, dataset.trainItem,
                                              self.num_users, self.num_items, self.device,
                                              split=int(config.get("csr_split", DEFAULT_SPLIT)),
@@ -97,6 +132,7 @@ class LightGCN(nn.Module):
         self.engine = PropagationEngine(self.graph, self.latent_dim, self.num_layers,
                                         int(config.get("bpr_batch_size", 2048)),
                                         prune=bool(config.get("prune", True)))
+        self.engine.edge_dropout = self.keep_prob if self.dropout else None
         self._loss_accum = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.test_item_emb = None
 
@@ -106,9 +142,28 @@ class LightGCN(nn.Module):
                                           device=self.device)
         nn.init.normal_(self.all_embedding.weight, std=0.1)
 
+    # ---------------------------------------------------------- edge dropout
+    def dropout_seed(self, step: int) -> int:
+        """The mask seed of the ``step``-th training step under dropout
+        (counted from 0 over stageOne / OneEpoch batches / training-mode
+        forwards alike): PropagationEngine.dropout_seed(config["seed"], step)
+        = (seed mod 2^32) * 2^32 + step mod 2^32, config["seed"] defaulting to
+        0.  It does not depend on the rank.  mirec_edge_keep_mask with this
+        seed and keep_prob restates the step's mask."""
+        return PropagationEngine.dropout_seed(int(self.config.get("seed", 0) or 0), step)
+
+    def _next_dropout(self):
+        """(keep_prob, seed) of the step about to run, advancing the counter;
+        None when dropout is off or the module is in eval mode."""
+        if not (self.dropout and self.training):
+            return None
+        d = (self.keep_prob, self.dropout_seed(self._drop_step))
+        self._drop_step += 1
+        return d
+
     # --------------------------------------------------------- reference API
     def forward(self):
-        out = _Propagate.apply(self.all_embedding.weight, self.engine)
+        out = _Propagate.apply(self.all_embedding.weight, self.engine, self._next_dropout())
         return out[: self.num_users], out[self.num_users:]
 
     def getEmbedding(self, users, pos_items, neg_items):
@@ -175,7 +230,7 @@ class LightGCN(nn.Module):
         w = self.all_embedding.weight
         return self.engine.train_step(w, self.optim, self._as_i32(user), self._as_i32(pos),
                                       self._as_i32(neg), float(self.config["decay"]),
-                                      loss_accum).clone()
+                                      loss_accum, dropout=self._next_dropout()).clone()
 
     @torch.no_grad()
     def OneEpoch(self, user, pos, neg):
@@ -188,7 +243,7 @@ class LightGCN(nn.Module):
         for i in range(0, n, B):
             self.engine.train_step(self.all_embedding.weight, self.optim, user[i:i + B],
                                    pos[i:i + B], neg[i:i + B], float(self.config["decay"]),
-                                   self._loss_accum)
+                                   self._loss_accum, dropout=self._next_dropout())
         return self._loss_accum[0] / total_batch
 
     # ------------------------------------------------------------- sampling
@@ -205,4 +260,15 @@ class LightGCN(nn.Module):
         return u, p, n
 
     def optimizer_state_dict(self):
-        return self.optim.state_dict()
+        """torch.optim.Adam's state_dict of the table, plus (with dropout on)
+        ``edge_dropout_step``, the position in the mask sequence."""
+        sd = self.optim.state_dict()
+        if self.dropout:
+            sd["edge_dropout_step"] = int(self._drop_step)
+        return sd
+
+    def load_optimizer_state_dict(self, sd: dict) -> None:
+        """Restore optimizer_state_dict(): a resumed run continues the Adam
+        moments and the mask sequence where the saved one stopped."""
+        self.optim.load_state_dict(sd)
+        self._drop_step = int(sd.get("edge_dropout_step", 0))

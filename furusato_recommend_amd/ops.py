@@ -20,7 +20,11 @@ the transposed one otherwise).  ``lgcn_propagate_w(x, edge_weight, graph)`` is
 the edge-weighted y = Â x on a graph built with weights
 (``Graph.from_edge_index(..., edge_weight=)``): its backward gives Âᵀ ȳ for
 ``x`` and, on a ``normalize=False`` graph, the per-edge dots
-ȳ[dst_e] · x[src_e] (mirec_edge_dot) for ``edge_weight``.  All have fake
+ȳ[dst_e] · x[src_e] (mirec_edge_dot) for ``edge_weight``.  ``lgcn_propagate_drop(x, graph, keep_prob, seed)`` is y = Â x
+with edge dropout (PyG's ``dropout_edge`` followed by ``LGConv``; the mask is
+a hash of (seed, destination, source) evaluated inside the kernel, restated
+by ``mirec_edge_keep_mask``); its backward is ``lgcn_propagate_drop_t``, the
+transposed mask on the same CSR.  All have fake
 (meta) implementations, so they trace under torch.compile / torch.export
 without running a kernel.
 Reference call sites: model/lgcn.py:66,82 (``LGConv()(x, edge_index)``).
@@ -59,13 +63,13 @@ def _graph(h: int):
     return g
 
 
-def _apply(g, x: torch.Tensor) -> torch.Tensor:
+def _apply(g, x: torch.Tensor, **drop) -> torch.Tensor:
     from .lgconv import _spmm  # width padding / column blocks for any D
     if x.device.type != "cuda" or x.dtype != torch.float32 or x.dim() != 2:
         raise ValueError("mirec.lgcn_propagate: float32 [N, D] tensor on the HIP device")
     if x.shape[0] != g.n_nodes:
         raise ValueError(f"mirec.lgcn_propagate: x has {x.shape[0]} rows, graph {g.n_nodes}")
-    return _spmm(g, x)
+    return _spmm(g, x, **drop)
 
 
 @torch.library.custom_op("mirec::lgcn_propagate", mutates_args=())
@@ -89,6 +93,70 @@ def _(x, graph):
 @lgcn_propagate_t.register_fake
 def _(x, graph):
     return torch.empty_like(x)
+
+
+# ---- edge dropout ---------------------------------------------------------------
+def _check_drop(g, keep_prob: float) -> None:
+    if not (0.0 < float(keep_prob) <= 1.0):
+        raise ValueError(f"mirec.lgcn_propagate_drop: keep_prob must lie in (0, 1], "
+                         f"got {keep_prob!r}")
+    if g.val is not None:
+        raise ValueError("mirec.lgcn_propagate_drop: edge dropout and edge weights are not "
+                         "combined")
+
+
+@torch.library.custom_op("mirec::lgcn_propagate_drop", mutates_args=())
+def lgcn_propagate_drop(x: torch.Tensor, graph: int, keep_prob: float, seed: int) -> torch.Tensor:
+    """y = Â_drop x: PyG's ``dropout_edge`` followed by ``LGConv`` in one
+    launch, with dinv of the full graph (the reference's __dropout_x drops
+    entries of the normalised matrix).  Entry (j → i) is kept iff
+    mirec_edge_keep(seed, i, j) (include/mirec.h; multi-edges share the draw)
+    and kept entries are divided by ``keep_prob``.  ``seed`` is taken modulo
+    2^64."""
+    g = _graph(graph)
+    _check_drop(g, keep_prob)
+    return _apply(g, x, dropout=(keep_prob, seed))
+
+
+@torch.library.custom_op("mirec::lgcn_propagate_drop_t", mutates_args=())
+def lgcn_propagate_drop_t(x: torch.Tensor, graph: int, keep_prob: float,
+                          seed: int) -> torch.Tensor:
+    """y = Â_dropᵀ x (the backward of lgcn_propagate_drop): the transposed
+    mask keep(seed, j, i) on the same CSR (the transposed one for an
+    asymmetric edge multiset)."""
+    g = _graph(graph)
+    _check_drop(g, keep_prob)
+    return _apply(g if g.symmetric else g.transpose, x, dropout=(keep_prob, seed),
+                  transposed=True)
+
+
+@lgcn_propagate_drop.register_fake
+def _(x, graph, keep_prob, seed):
+    return torch.empty_like(x)
+
+
+@lgcn_propagate_drop_t.register_fake
+def _(x, graph, keep_prob, seed):
+    return torch.empty_like(x)
+
+
+def _setup_drop(ctx, inputs, output):
+    ctx.graph_obj = _graph(inputs[1])
+    ctx.drop = (float(inputs[2]), int(inputs[3]))
+
+
+def _bwd_drop(ctx, grad):
+    return (torch.ops.mirec.lgcn_propagate_drop_t(grad.contiguous(), handle(ctx.graph_obj),
+                                                  *ctx.drop), None, None, None)
+
+
+def _bwd_drop_t(ctx, grad):
+    return (torch.ops.mirec.lgcn_propagate_drop(grad.contiguous(), handle(ctx.graph_obj),
+                                                *ctx.drop), None, None, None)
+
+
+lgcn_propagate_drop.register_autograd(_bwd_drop, setup_context=_setup_drop)
+lgcn_propagate_drop_t.register_autograd(_bwd_drop_t, setup_context=_setup_drop)
 
 
 # ---- edge-weighted propagation ------------------------------------------------
@@ -205,4 +273,5 @@ def _bwd_t(ctx, grad):
 lgcn_propagate.register_autograd(_bwd, setup_context=_setup)
 lgcn_propagate_t.register_autograd(_bwd_t, setup_context=_setup)
 
-__all__ = ["handle", "lgcn_propagate", "lgcn_propagate_t", "lgcn_propagate_w"]
+__all__ = ["handle", "lgcn_propagate", "lgcn_propagate_t", "lgcn_propagate_w",
+           "lgcn_propagate_drop", "lgcn_propagate_drop_t"]

@@ -20,7 +20,10 @@ from .lightgcn import LightGCN
 
 
 class rAdjGCN(LightGCN):  # noqa: N801  (the reference's class name)
-    """model/radj.py:47-154 on MI355X."""
+    """model/radj.py:47-154 on MI355X.  ``config["dropout"]`` is refused
+    (ValueError): edge dropout and the scales are not combined."""
+
+    edge_dropout_supported = False
 
     def _graph_r(self, config) -> float:
         return float(config.get("r", 0.5))

@@ -98,6 +98,9 @@ def wrap(model, group=None, mode: str | None = None, **kw):
     ``DenseGradDataParallel`` for the autograd models (``mode`` = the id
     table's exchange)."""
     from .dist import DataParallel, DenseGradDataParallel, HostDataParallel
+    if getattr(model, "dropout", False) is True and hasattr(model, "all_embedding"):
+        raise NotImplementedError("data-parallel training of a LightGCN with edge dropout "
+                                  "(config['dropout']) is not implemented")
     if hasattr(model, "engine") and hasattr(model, "all_embedding"):
         return DataParallel(model.engine, model.all_embedding.weight.data, model.optim,
                             group=group, mode=mode or "auto", **kw)

@@ -39,7 +39,9 @@ extern "C" {
  * weights) after the version was set; a binding checks its mirror of the
  * struct with mirec_struct_sizes, and a NULL `val` is the earlier behaviour.
  * Likewise mirec_prop_t's trailing scale_src / scale_dst / scale_next: NULL
- * (each on its own) means csr->dinv, the earlier behaviour. */
+ * (each on its own) means csr->dinv, the earlier behaviour.  Edge dropout
+ * left both structs alone: it has a struct and an entry point of its own
+ * (mirec_drop_t, mirec_propagate_drop). */
 #define MIREC_ABI_VERSION 1
 
 enum mirec_status {
@@ -245,6 +247,55 @@ typedef struct mirec_prop {
 
 int mirec_propagate(const mirec_csr_t *csr, const mirec_prop_t *p,
                     mirec_stream_t stream);
+
+/* Edge dropout (the reference's LightGCN.__dropout_x, model/MF.py:158-176):
+ * while training, every entry of the normalised adjacency is kept with
+ * probability keep_prob and the kept ones are divided by keep_prob.  Here the
+ * mask is a pure function of (seed, destination, source), evaluated inside
+ * the propagation kernel for the row it walks and the column it has loaded,
+ * so no mask or value array exists and the transposed matrix (the backward)
+ * needs no second CSR: it is the same function with i and j swapped.  With
+ *   mix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *             x = (x ^ (x >> 27)) * 0x94D049BB133111EB; return x ^ (x >> 31)
+ *             (uint64 arithmetic, the splitmix64 finaliser)
+ *   key = mix64(seed ^ 0xD6E8FEB86659FD93)
+ *   t   = floor((double)keep_prob * 2^32), clamped to [1, 2^32]
+ * entry (j -> i) (source j = col[e], destination i = its row) is kept iff
+ *   mirec_edge_keep(seed, i, j) := (mix64(key ^ ((uint64)i << 32 | j)) >> 32) < t.
+ * keep(seed, i, j) and keep(seed, j, i) are independent draws: the dropped
+ * matrix is not symmetric.  Multi-edges (several entries with the same i and
+ * j) share ONE draw: all are kept or all dropped, as in the reference, whose
+ * coalesced sparse tensor holds one value per (i, j).  keep_prob must lie in
+ * (0, 1]; 1 keeps every entry (t = 2^32 is compared without wrapping).
+ *
+ * Host: keep[e] = mirec_edge_keep(seed, i, col[e]) for every entry e of every
+ * row i of a host CSR; transposed != 0: keep[e] = mirec_edge_keep(seed,
+ * col[e], i), the mask a launch with drop->transposed applies.  keep: [nnz]
+ * bytes (0 / 1).  MIREC_ERR_ARG for keep_prob outside (0, 1] or NaN. */
+int mirec_edge_keep_mask(const int64_t *rowptr, const int32_t *col, int64_t n_rows,
+                         uint64_t seed, float keep_prob, int32_t transposed,
+                         uint8_t *keep);
+
+/* The dropout of one launch.  All zero (or a NULL pointer) = no dropout. */
+typedef struct mirec_drop {
+  float keep_prob;     /* in (0, 1]; 0 = off */
+  int32_t transposed;  /* != 0: the mask of the transposed matrix */
+  uint64_t seed;
+} mirec_drop_t;
+
+size_t mirec_drop_sizeof(void);
+
+/* mirec_propagate on the edge-dropped matrix: the sum over row i runs over
+ * the entries (j -> i) with mirec_edge_keep(seed, i, j) (drop->transposed:
+ * (seed, j, i)) only, in CSR order, and is multiplied by 1 / keep_prob; dinv
+ * and the epilogue are those of the full graph.  Every in_mode, mask, row
+ * list, long-row segments and the fused Adam apply; a dropped neighbour's row
+ * is not read.  drop == NULL or drop->keep_prob == 0 is exactly
+ * mirec_propagate.  Refused (MIREC_ERR_ARG, nothing launched) with csr->val,
+ * with any scale vector of `p`, and for keep_prob outside (0, 1] or NaN.
+ * The launch always runs the row kernel: there is no swept form. */
+int mirec_propagate_drop(const mirec_csr_t *csr, const mirec_prop_t *p,
+                         const mirec_drop_t *drop, mirec_stream_t stream);
 
 /* Column-sweep layout of a block of CSR rows (the item rows of a bipartite
  * graph), built once per graph on the host (csrc/graph.cpp) and read by the
