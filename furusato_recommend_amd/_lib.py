@@ -93,6 +93,13 @@ class SweepWave(Structure):
     ]
 
 
+class SweepPace(Structure):
+    """mirec_sweep_pace_t (per-XCD pacing of the per-wave sweep; index 0 the
+    item launch, 1 the user launch)."""
+    _fields_ = [("ws", c_void_p), ("lead_bands", c_int32 * 2), ("every", c_int32 * 2),
+                ("nap", c_int32 * 2)]
+
+
 class RowGradGroup(Structure):
     """mirec_row_grad_group_t (one group of table-gradient row contributions)."""
     _fields_ = [
@@ -140,6 +147,13 @@ SIGNATURES = {
                                        c_int32, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
     "mirec_propagate_sweep_wave": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(SweepWave),
                                            POINTER(SweepWave), c_void_p]),
+    "mirec_sweep_pace_sizeof": (c_size_t, []),
+    "mirec_sweep_pace_ws_bytes": (c_size_t, []),
+    "mirec_propagate_sweep_wave_paced": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(SweepWave),
+                                                 POINTER(SweepWave), POINTER(SweepPace),
+                                                 c_void_p]),
+    "mirec_sweep_wave_stamp": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(SweepWave), c_void_p,
+                                       c_int64, c_void_p, c_void_p]),
     "mirec_drop_sizeof": (c_size_t, []),
     "mirec_propagate_drop": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(Drop), c_void_p]),
     "mirec_edge_keep_mask": (c_int, [c_void_p, c_void_p, c_int64, c_uint64, c_float, c_int32,
@@ -402,6 +416,8 @@ def _load():
         raise ImportError("struct layout mismatch: mirec_sweep_t")
     if lib.mirec_sweep_wave_sizeof() != ctypes.sizeof(SweepWave):
         raise ImportError("struct layout mismatch: mirec_sweep_wave_t")
+    if lib.mirec_sweep_pace_sizeof() != ctypes.sizeof(SweepPace):
+        raise ImportError("struct layout mismatch: mirec_sweep_pace_t")
     return lib
 
 

@@ -512,9 +512,10 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void prop_finalize(PropK a, co
 // ISSUED, nothing is handed over through memory), so a workgroup's waves stay
 // within a band of each other while row loads stay in flight across the band
 // boundary.  Every wave executes exactly n_bands - 1 barriers whatever its
-// streams hold.  Workgroups never wait for each other: they stay together
-// only because they start together and carry equal work per band; nothing
-// depends on which of them are resident.
+// streams hold.  Workgroups never wait for each other and nothing depends on
+// which of them are resident; nothing holds them together either (measured,
+// they drift tens of bands apart: the per-wave form below has an optional
+// per-XCD pacing for that).
 constexpr int kSweepThreads = 512;
 constexpr int kSweepLdsMax = 64 * 1024;
 
@@ -676,8 +677,55 @@ struct SweepWaveK {
   int32_t n_bands;
 };
 
-template <int D, int U, bool SCALED>
-__device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK &s) {
+// Two optional instantiations beside the production one (AUX = kAuxNone,
+// whose code they leave as it is):
+//
+// kAuxPace, per-XCD pacing.  Between workgroups nothing holds the window of
+// source rows together; here wave 0 of a workgroup, at its band advance and
+// before the band's s_barrier, adds to its XCD's sum of advances and naps
+// while its own count leads the XCD's mean (sum / registered workgroups) by
+// more than `lead` bands.  The nap loop runs at most kPaceMaxNaps times: no
+// workgroup ever waits UNTIL anything, so a launch ends whatever the
+// workspace holds and whichever workgroups are resident; a stale or wrong
+// figure costs time only.  The workspace is touched with non-returning
+// vector atomics and read through the scalar data cache (lgkmcnt), so the
+// row loads' vmcnt waits never see it.  A leaving workgroup takes its share
+// out of the sum and the count; the last one to leave zeroes the region.
+//
+// kAuxStamp, a measurement: wave 0 notes wall_clock64() in LDS at the tile's
+// start, at every band advance and at the tile's end, and writes the notes
+// out after the tile's epilogue with the workgroup's index and XCC id.
+constexpr int kAuxNone = 0, kAuxPace = 1, kAuxStamp = 2;
+constexpr int kPaceLabels = 8;          // XCC ids
+constexpr int kPaceLineWords = 32;      // one 128-B line per counter
+constexpr int kPaceRegionWords = (2 * kPaceLabels + 1) * kPaceLineWords;
+constexpr int kPaceMaxNaps = 8;         // polls (and naps) per paced advance
+constexpr int kPaceMaxNapUnits = 16;    // s_sleep 8 (512 clocks) per nap, at most
+constexpr int kXccIdReg = 20 | (3 << 11);  // hwreg(HW_REG_XCC_ID, 0, 4)
+
+struct SweepAuxK {
+  unsigned *ws;        // kAuxPace: this launch's region, kPaceRegionWords words
+  int32_t lead;
+  int32_t every;
+  int32_t nap;
+  long long *stamps;   // kAuxStamp: [n_tiles][n_bands + 1]
+  int32_t *meta;       // kAuxStamp: [n_tiles][2] = workgroup, XCC id
+};
+
+// One dword through the scalar data cache, bypassing it (glc): served by the
+// L2, counted by lgkmcnt.
+__device__ __forceinline__ unsigned pace_read(const unsigned *p) {
+  unsigned v;
+  asm volatile("s_load_dword %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(v)
+               : "s"(p)
+               : "memory");
+  return v;
+}
+
+template <int D, int U, bool SCALED, int AUX = kAuxNone>
+__device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK &s,
+                                                const SweepAuxK &x = SweepAuxK{}) {
   constexpr int LPR = D / 4;
   constexpr int G = 64 / LPR;          // lane groups = slots per step
   constexpr int NB = 64 / (U * G);     // batches per 64-slot chunk
@@ -690,8 +738,49 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long long kPadRow = (long long)0xffffffff00000000ull;
   const int64_t last = s.n_slots - 1;  // >= 0 (checked by the host)
+  // kAuxPace (wave 0): band advances of this workgroup since the kernel's
+  // start, how many of them the XCD's sum holds, advances until the next poll
+  int adv = 0, told = 0, due = 0;
+  unsigned *pace_reg = nullptr, *pace_sum = nullptr;
+  if constexpr (AUX == kAuxPace) {
+    const int label = (int)__builtin_amdgcn_s_getreg(kXccIdReg) & (kPaceLabels - 1);
+    pace_reg = x.ws + (2 * label) * kPaceLineWords;
+    pace_sum = pace_reg + kPaceLineWords;
+    due = x.every;
+    if (wid == 0 && lane == 0)
+      (void)__hip_atomic_fetch_add(pace_reg, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // wave 0, before the barrier of a band advance
+  auto pace = [&]() {
+    if constexpr (AUX == kAuxPace) {
+      if (wid != 0) return;
+      ++adv;
+      if (--due != 0) return;
+      due = x.every;
+      if (lane == 0)
+        (void)__hip_atomic_fetch_add(pace_sum, (unsigned)(adv - told), __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT);
+      told = adv;
+#pragma unroll 1
+      for (int i = 0; i < kPaceMaxNaps; ++i) {  // a constant trip count: never a wait-until
+        const long long sum = pace_read(pace_sum), reg = pace_read(pace_reg);
+        if ((long long)(adv - x.lead) * reg <= sum) break;  // lead <= x.lead (or no count yet)
+#pragma unroll 1
+        for (int j = 0; j < x.nap; ++j) __builtin_amdgcn_s_sleep(8);
+      }
+    }
+  };
+  [[maybe_unused]] long long *stamp_lds = nullptr;
+  if constexpr (AUX == kAuxStamp)
+    stamp_lds = reinterpret_cast<long long *>(sweep_acc + (int64_t)s.tile_rows * LPR);
+  auto stamp = [&](int i) {
+    if constexpr (AUX == kAuxStamp) {
+      if (wid == 0 && lane == 0) stamp_lds[i] = (long long)wall_clock64();
+    }
+  };
 #pragma unroll 1
   for (int tile = blockIdx.x; tile < s.n_tiles; tile += gridDim.x) {
+    stamp(0);
     const int64_t tile_row0 = (int64_t)tile * s.tile_rows;
     const int tile_len = (int)min((int64_t)s.tile_rows, s.n_rows - tile_row0);
     const int lr0 = min(wid * s.wave_rows, tile_len);
@@ -725,9 +814,11 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
         // beyond the current one (batches past the end decide nothing)
         const int nc = __builtin_amdgcn_readlane(ccol, k * U * G);
         while (b0 + k < n_batches && band + 1 < s.n_bands && (int64_t)nc >= hi) {
+          pace();
           __builtin_amdgcn_s_barrier();
           ++band;
           hi += s.band_rows;
+          stamp(band);
         }
         float4 v[U];
         int r[U];
@@ -757,8 +848,10 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
       cur = nxt;
     }
     while (band + 1 < s.n_bands) {  // every wave executes the same number of barriers
+      pace();
       __builtin_amdgcn_s_barrier();
       ++band;
+      stamp(band);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -770,7 +863,36 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
     // rows are private to their wave
     for (int lr = lr0 + g; lr < lr1; lr += G)
       row_epilogue<D, SCALED>(a, s.row0 + tile_row0 + lr, sweep_acc[lr * LPR + sub], sub);
+    if constexpr (AUX == kAuxStamp) {
+      stamp(s.n_bands);
+      if (wid == 0) {  // (a wave's LDS instructions complete in order)
+        long long *o = x.stamps + (int64_t)tile * (s.n_bands + 1);
+        for (int b = lane; b <= s.n_bands; b += 64) o[b] = stamp_lds[b];
+        if (lane == 0) {
+          x.meta[2 * tile] = (int32_t)blockIdx.x;
+          x.meta[2 * tile + 1] = (int32_t)__builtin_amdgcn_s_getreg(kXccIdReg);
+        }
+      }
+    }
     __syncthreads();  // the accumulators are reused by the workgroup's next tile
+  }
+  if constexpr (AUX == kAuxPace) {
+    // leave: take this workgroup out of its XCD's mean; the last workgroup
+    // of the launch to leave zeroes the region for the next launch
+    if (wid == 0 && lane == 0) {
+      (void)__hip_atomic_fetch_add(pace_sum, 0u - (unsigned)told, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+      (void)__hip_atomic_fetch_add(pace_reg, 0u - 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's adds are done
+      unsigned *done = x.ws + 2 * kPaceLabels * kPaceLineWords;
+      const unsigned left = __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);
+      if (left == gridDim.x - 1) {
+        for (int i = 0; i <= 2 * kPaceLabels; ++i)
+          __hip_atomic_store(x.ws + i * kPaceLineWords, 0u, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
   }
 }
 
@@ -778,6 +900,12 @@ template <int D, int U, bool SCALED>
 __global__ __launch_bounds__(kSweepThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 MIREC_NO_PK_F32 void prop_sweep_wave_kernel(PropK a, SweepWaveK s) {
   sweep_wave_work<D, U, SCALED>(a, s);
+}
+
+template <int D, int U, bool SCALED, int AUX>
+__global__ __launch_bounds__(kSweepThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+MIREC_NO_PK_F32 void prop_sweep_wave_aux_kernel(PropK a, SweepWaveK s, SweepAuxK x) {
+  sweep_wave_work<D, U, SCALED, AUX>(a, s, x);
 }
 
 using PropFn = void (*)(PropK);
@@ -1023,8 +1151,24 @@ static bool sweep_wave_valid(const mirec_csr_t *c, const mirec_sweep_wave_t *w, 
   return w->grid > 0 && w->grid <= w->n_tiles;
 }
 
+// The stamping launch's buffers (mirec_sweep_wave_stamp).
+struct SweepStamp {
+  const mirec_sweep_wave_t *layout;
+  int64_t *stamps;
+  int64_t stamps_len;
+  int32_t *meta;
+};
+
+static int32_t sweep_wave_bands(const mirec_sweep_wave_t *w) {
+  return (int32_t)std::max<int64_t>(1, (w->n_src + w->band_rows - 1) / w->band_rows);
+}
+
+// `pace` with block = 0 (items) or 1 (users): that block's region and
+// parameters (every == 0: the block runs unpaced); `stamp`: the measurement.
 template <int D>
-static int launch_sweep_wave(const PropK &k, const mirec_sweep_wave_t *w, hipStream_t st) {
+static int launch_sweep_wave(const PropK &k, const mirec_sweep_wave_t *w, hipStream_t st,
+                             const mirec_sweep_pace_t *pace = nullptr, int block = 0,
+                             const SweepStamp *stamp = nullptr) {
   SweepWaveK s;
   s.wptr = w->wptr;
   s.slot = reinterpret_cast<const long long *>(w->slot);
@@ -1036,11 +1180,35 @@ static int launch_sweep_wave(const PropK &k, const mirec_sweep_wave_t *w, hipStr
   s.wave_rows = w->wave_rows;
   s.n_tiles = w->n_tiles;
   s.band_rows = w->band_rows;
-  s.n_bands = (int32_t)std::max<int64_t>(1, (w->n_src + w->band_rows - 1) / w->band_rows);
-  const size_t lds = (size_t)w->tile_rows * D * sizeof(float);
-  const auto kernel = k.scale_next != nullptr ? prop_sweep_wave_kernel<D, 4, true>
-                                              : prop_sweep_wave_kernel<D, 4, false>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)w->grid), dim3(kSweepThreads), lds, st, k, s);
+  s.n_bands = sweep_wave_bands(w);
+  size_t lds = (size_t)w->tile_rows * D * sizeof(float);
+  const bool scaled = k.scale_next != nullptr;
+  if (stamp != nullptr) {
+    SweepAuxK x = {};
+    x.stamps = reinterpret_cast<long long *>(stamp->stamps);
+    x.meta = stamp->meta;
+    lds += (size_t)(s.n_bands + 1) * sizeof(long long);
+    const auto kernel = scaled ? prop_sweep_wave_aux_kernel<D, 4, true, kAuxStamp>
+                               : prop_sweep_wave_aux_kernel<D, 4, false, kAuxStamp>;
+    if (lds > (size_t)kSweepLdsMax &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return MIREC_ERR_HIP;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)w->grid), dim3(kSweepThreads), lds, st, k, s, x);
+  } else if (pace != nullptr && pace->every[block] > 0) {
+    SweepAuxK x = {};
+    x.ws = reinterpret_cast<unsigned *>(pace->ws) + block * kPaceRegionWords;
+    x.lead = pace->lead_bands[block];
+    x.every = pace->every[block];
+    x.nap = pace->nap[block];
+    const auto kernel = scaled ? prop_sweep_wave_aux_kernel<D, 4, true, kAuxPace>
+                               : prop_sweep_wave_aux_kernel<D, 4, false, kAuxPace>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)w->grid), dim3(kSweepThreads), lds, st, k, s, x);
+  } else {
+    const auto kernel = scaled ? prop_sweep_wave_kernel<D, 4, true>
+                               : prop_sweep_wave_kernel<D, 4, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)w->grid), dim3(kSweepThreads), lds, st, k, s);
+  }
   MIREC_LAUNCH_CHECK();
   return MIREC_OK;
 }
@@ -1057,8 +1225,16 @@ namespace mirec {
 // form) and `wi` (wave form, `wu` optional beside it) is given.
 static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sweep_t *sw,
                      const mirec_sweep_wave_t *wi, const mirec_sweep_wave_t *wu,
-                     mirec_stream_t stream, const mirec_drop_t *drop = nullptr) {
+                     mirec_stream_t stream, const mirec_drop_t *drop = nullptr,
+                     const mirec_sweep_pace_t *pace = nullptr,
+                     const SweepStamp *stamp = nullptr) {
   MIREC_CHECK_ARG(c != nullptr && p != nullptr);
+  if (pace != nullptr) {
+    MIREC_CHECK_ARG(pace->ws != nullptr);
+    for (int b = 0; b < 2; ++b)
+      MIREC_CHECK_ARG(pace->every[b] >= 0 && pace->lead_bands[b] >= 0 && pace->nap[b] >= 0 &&
+                      pace->nap[b] <= kPaceMaxNapUnits);
+  }
   MIREC_CHECK_ARG(c->rowptr != nullptr && c->dinv != nullptr && c->n_rows >= 0);
   MIREC_CHECK_ARG(c->nnz == 0 || c->col != nullptr);
   if (!dim_supported(p->dim)) return MIREC_ERR_DIM;
@@ -1139,12 +1315,22 @@ static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sw
   }
   const int64_t cap = p->row_list_cap;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (stamp != nullptr) {
+    // the measurement: one block's launch, nothing else (its other rows stay unwritten)
+    const mirec_sweep_wave_t *w = stamp->layout;
+    MIREC_CHECK_ARG(w != nullptr && stamp->stamps != nullptr && stamp->meta != nullptr);
+    MIREC_CHECK_ARG(sweep_launch_qualifies(c, p) && w->row0 >= 0 && w->n_rows > 0 &&
+                    w->row0 + w->n_rows <= c->n_rows &&
+                    sweep_wave_valid(c, w, w->row0, w->n_rows));
+    MIREC_CHECK_ARG(stamp->stamps_len >= (int64_t)w->n_tiles * (sweep_wave_bands(w) + 1));
+    return launch_sweep_wave<64>(k, w, st, nullptr, 0, stamp);
+  }
   if (sweep_qualifies(c, p, sw)) return launch_sweep<64, 4>(c, k, sw, st);
   if (wi != nullptr && sweep_launch_qualifies(c, p) &&
       sweep_wave_valid(c, wi, wi->row0, c->n_rows - wi->row0)) {
-    const int rc = launch_sweep_wave<64>(k, wi, st);
+    const int rc = launch_sweep_wave<64>(k, wi, st, pace, 0);
     if (rc != MIREC_OK || wi->row0 == 0) return rc;
-    if (sweep_wave_valid(c, wu, 0, wi->row0)) return launch_sweep_wave<64>(k, wu, st);
+    if (sweep_wave_valid(c, wu, 0, wi->row0)) return launch_sweep_wave<64>(k, wu, st, pace, 1);
     return launch_head<64, 4>(c, k, wi->row0, st);
   }
   switch (p->dim) {
@@ -1176,6 +1362,27 @@ extern "C" int mirec_propagate_sweep_wave(const mirec_csr_t *c, const mirec_prop
                                           const mirec_sweep_wave_t *users,
                                           mirec_stream_t stream) {
   return mirec::propagate(c, p, nullptr, items, users, stream);
+}
+
+extern "C" size_t mirec_sweep_pace_sizeof(void) { return sizeof(mirec_sweep_pace_t); }
+
+extern "C" size_t mirec_sweep_pace_ws_bytes(void) {
+  return 2 * (size_t)mirec::kPaceRegionWords * sizeof(unsigned);
+}
+
+extern "C" int mirec_propagate_sweep_wave_paced(const mirec_csr_t *c, const mirec_prop_t *p,
+                                                const mirec_sweep_wave_t *items,
+                                                const mirec_sweep_wave_t *users,
+                                                const mirec_sweep_pace_t *pace,
+                                                mirec_stream_t stream) {
+  return mirec::propagate(c, p, nullptr, items, users, stream, nullptr, pace);
+}
+
+extern "C" int mirec_sweep_wave_stamp(const mirec_csr_t *c, const mirec_prop_t *p,
+                                      const mirec_sweep_wave_t *layout, int64_t *stamps,
+                                      int64_t stamps_len, int32_t *meta, mirec_stream_t stream) {
+  const mirec::SweepStamp s = {layout, stamps, stamps_len, meta};
+  return mirec::propagate(c, p, nullptr, nullptr, nullptr, stream, nullptr, nullptr, &s);
 }
 
 extern "C" size_t mirec_drop_sizeof(void) { return sizeof(mirec_drop_t); }

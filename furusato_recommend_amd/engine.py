@@ -50,6 +50,11 @@ from .graph import Graph
 # measurements of DESIGN.md §14.
 SWEEP_FORM = "wave"
 SWEEP_USERS = True
+# Defaults of PropagationEngine.layer_sum_rows and sweep_pace:
+# the layer sum of a pruned forward on S only; the sweep's per-XCD pacing
+# (None, or a dict(lead_bands, every, nap) per block "items" / "users").
+LAYER_SUM_ROWS = "self"
+SWEEP_PACE = {"items": (8, 16, 16), "users": (4, 4, 16)}
 
 
 def prop_launch_bytes(in_mode: int, n_nodes: int, nnz: int, dim: int, *, slot=False,
@@ -294,6 +299,9 @@ class PropagationEngine:
         # tuning switches (tools/bench_variants.py)
         self.use_hop_list = True      # F1 launches walk hop_list (else: byte map)
         self.reuse_prescaled = True   # fused update writes the next x~_0
+        # rows on which a pruned forward keeps the layer sum below the last
+        # layer: "self" = S (all the loss reads), "hop" = F1 through layer L-1
+        self.layer_sum_rows = LAYER_SUM_ROWS
         # full PRESCALED launches gather the item rows with the column sweep
         # (graphs that qualify, Graph.sweep_layout; else the row kernel; an
         # edge-weighted graph never does: every launch below then runs the
@@ -307,6 +315,10 @@ class PropagationEngine:
         self._wave_sizes = {"items": (None, None), "users": (None, None), "max_grid": None}
         self.sweep_wave = self.sweep_wave_users = None
         self._sweep_form, self._sweep_users = SWEEP_FORM, SWEEP_USERS
+        # per-XCD pacing of the wave form's launches: None, or
+        # {"items": (lead_bands, every, nap) | None, "users": ... | None}
+        self.sweep_pace = SWEEP_PACE
+        self._pace_ws = None
         self._wave_layouts()
         # first backward layer's neighbour filter: "slot" (one dependent load;
         # best for one batch), "bytemap" (S byte map, then the slot of the
@@ -391,7 +403,7 @@ class PropagationEngine:
     def _prop(self, *, in_mode, x_in=None, seed_in=None, seed=None, addend=None, seed2=None,
               divisor=1.0, out=None, xs_out=None, adam=None, param=None, graph=None,
               row_mask=None, in_mask=None, row_list=None, row_count=None, row_list_cap=0,
-              out_mask=None, wide_list=None, wide_count=None, direction="fwd"):
+              out_mask=None, wide_list=None, wide_count=None, direction="fwd", stamp=None):
         """One propagation launch.  ``direction`` matters on an r-adjusted
         graph only (scales a = deg^-r, b = deg^-(1-r); otherwise the three
         scale pointers stay NULL = dinv): "fwd" applies Â = D_b A D_a and
@@ -443,7 +455,13 @@ class PropagationEngine:
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record()
         on = self.use_sweep and g is self.g
-        if self._drop is not None:
+        if stamp is not None:
+            # the drift measurement (sweep_stamp): one block's stamping launch
+            lay, stamps, meta = stamp
+            check(lib.mirec_sweep_wave_stamp(g.csr_ptr(), ctypes.byref(p), lay.ptr(),
+                                             stamps.data_ptr(), stamps.numel(), meta.data_ptr(),
+                                             _lib.stream_handle()), "sweep_wave_stamp")
+        elif self._drop is not None:
             # a dropped launch has an entry point of its own (and no swept form)
             if direction not in ("fwd", "bwd", "bwd_last"):
                 raise ValueError(f"direction: 'fwd', 'bwd' or 'bwd_last', got {direction!r}")
@@ -453,10 +471,12 @@ class PropagationEngine:
                                            _lib.stream_handle()), "propagate_drop")
         elif on and self._sweep_form == "wave":
             wi, wu = self.sweep_wave, self.sweep_wave_users if self._sweep_users else None
-            check(lib.mirec_propagate_sweep_wave(g.csr_ptr(), ctypes.byref(p),
-                                                 wi.ptr() if wi is not None else None,
-                                                 wu.ptr() if wu is not None else None,
-                                                 _lib.stream_handle()), "propagate")
+            pace = self._pace_struct()
+            check(lib.mirec_propagate_sweep_wave_paced(
+                g.csr_ptr(), ctypes.byref(p), wi.ptr() if wi is not None else None,
+                wu.ptr() if wu is not None else None,
+                ctypes.byref(pace) if pace is not None else None, _lib.stream_handle()),
+                "propagate")
         else:
             sw = self.sweep if on else None
             check(lib.mirec_propagate_sweep(g.csr_ptr(), ctypes.byref(p),
@@ -466,6 +486,38 @@ class PropagationEngine:
             e.record()
             kind = (in_mode, in_mask is not None, row_mask is not None, out_mask is not None)
             ev.append((s, e, kind, self.launch_bytes(p, g)))
+
+    def _pace_struct(self):
+        """mirec_sweep_pace_t of ``sweep_pace`` (None: unpaced): a dict with
+        (lead_bands, every, nap) or None under "items" and "users".  The
+        workspace is zeroed once, here; the launches re-zero it themselves."""
+        sp = self.sweep_pace
+        if sp is None:
+            return None
+        if self._pace_ws is None:
+            self._pace_ws = torch.zeros(int(lib.mirec_sweep_pace_ws_bytes()) // 4,
+                                        dtype=torch.int32, device=self.g.device)
+        pace = _lib.SweepPace(ws=self._pace_ws.data_ptr())
+        for b, block in enumerate(("items", "users")):
+            lead, every, nap = sp.get(block) or (0, 0, 0)
+            pace.lead_bands[b], pace.every[b], pace.nap[b] = int(lead), int(every), int(nap)
+        return pace
+
+    def sweep_stamp(self, block: str, **launch):
+        """Debug: run the wave-form launch of one block ("items" / "users")
+        with the stamping kernel (tools/sweep_drift.py) and the propagation
+        arguments ``launch`` (as _prop's).  Returns (stamps [tiles, bands + 1]
+        int64 of wall_clock64 ticks: tile start, band advances, tile end;
+        meta [tiles, 2] int32: workgroup, XCC id)."""
+        lay = self.sweep_wave if block == "items" else self.sweep_wave_users
+        if lay is None:
+            raise RuntimeError(f"no wave-form layout of the {block} block")
+        d = lay.desc
+        bands = max(1, -(-d.n_src // d.band_rows))
+        stamps = torch.zeros(d.n_tiles, bands + 1, dtype=torch.int64, device=self.g.device)
+        meta = torch.zeros(d.n_tiles, 2, dtype=torch.int32, device=self.g.device)
+        self._prop(stamp=(lay, stamps, meta), **launch)
+        return stamps, meta
 
     def launch_bytes(self, p: Prop, g: Graph) -> int:
         """Algorithmic bytes of a launch over every row.  With an out_mask the
@@ -687,6 +739,8 @@ class PropagationEngine:
         (valid until the next call)."""
         L = self.L
         self._acc_full = None
+        if self.layer_sum_rows not in ("self", "hop"):
+            raise ValueError(f"layer_sum_rows: 'self' or 'hop', got {self.layer_sum_rows!r}")
         if L == 0:
             self.acc.copy_(emb)
             self._acc_full = self._token(emb)
@@ -705,8 +759,12 @@ class PropagationEngine:
                 rows = self._self_rows()
             elif pruned and l == L - 1:  # F1 = S ∪ N(S)
                 rows = self._hop_rows()
-            if pruned and l == L - 2:
-                # the layer sum is read next by layer L-1, on F1 rows only
+            if pruned and l < L and self.layer_sum_rows == "self":
+                # the layer sum is read by the loss alone, on S: every layer
+                # below the last adds to `acc` on the rows of S only
+                rows["out_mask"] = self.bm_self
+            elif pruned and l == L - 2:
+                # ("hop": the layer sum kept on every F1 row through layer L-1)
                 rows["out_mask"] = self.bm_hop
             self._prop(in_mode=IN_PRESCALED,
                        x_in=self.x0s if l == 1 else self.xs[(l - 2) % 2],

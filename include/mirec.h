@@ -416,6 +416,45 @@ int mirec_propagate_sweep_wave(const mirec_csr_t *csr, const mirec_prop_t *p,
                                const mirec_sweep_wave_t *items,
                                const mirec_sweep_wave_t *users, mirec_stream_t stream);
 
+/* Per-XCD pacing of the per-wave sweep.  Index 0 of each array is the item
+ * launch's, index 1 the user launch's; every[b] == 0 leaves that launch
+ * unpaced.  One wave per workgroup, on every every[b]-th band advance and
+ * before the band's barrier, adds its advances to its XCD's sum and naps
+ * (nap[b] units of 512 clocks, 0 .. 16) while its own count of advances
+ * leads the XCD's mean by more than lead_bands[b]; it polls a fixed number
+ * of times at most and never waits until anything, so a launch ends whatever
+ * `ws` holds.  Results do not depend on the pacing by a bit.  `ws`: device
+ * memory of mirec_sweep_pace_ws_bytes() bytes, zeroed once by the caller; the
+ * last workgroup of a launch to leave zeroes its region again (the two
+ * launches use separate regions). */
+typedef struct mirec_sweep_pace {
+  void *ws;
+  int32_t lead_bands[2];
+  int32_t every[2];
+  int32_t nap[2];
+} mirec_sweep_pace_t;
+
+size_t mirec_sweep_pace_sizeof(void);
+size_t mirec_sweep_pace_ws_bytes(void);
+
+/* mirec_propagate_sweep_wave with its sweep launches paced.  Same qualifying
+ * rule; pace == NULL is exactly mirec_propagate_sweep_wave. */
+int mirec_propagate_sweep_wave_paced(const mirec_csr_t *csr, const mirec_prop_t *p,
+                                     const mirec_sweep_wave_t *items,
+                                     const mirec_sweep_wave_t *users,
+                                     const mirec_sweep_pace_t *pace, mirec_stream_t stream);
+
+/* A measurement, not a propagation entry: the sweep launch of ONE block
+ * (`layout`, items or users) with wave 0 of every workgroup noting
+ * wall_clock64() at the tile's start, at each band advance and at the tile's
+ * end.  stamps: [n_tiles][n_bands + 1] (n_bands = ceil(n_src / band_rows),
+ * stamps_len >= that many elements), meta: [n_tiles][2] = workgroup index and
+ * XCC id of the workgroup that ran the tile.  The launch must qualify
+ * (MIREC_ERR_ARG otherwise); rows outside the block are not written. */
+int mirec_sweep_wave_stamp(const mirec_csr_t *csr, const mirec_prop_t *p,
+                           const mirec_sweep_wave_t *layout, int64_t *stamps,
+                           int64_t stamps_len, int32_t *meta, mirec_stream_t stream);
+
 /* out[e] = sum_c a[row(e), c] * b[col[e], c] for every entry e of the CSR, in
  * CSR order (row(e) = the row whose range holds e): with a = dL/dy and b = x
  * the gradient of y = A x with respect to the entry values (csr->val itself

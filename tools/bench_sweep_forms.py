@@ -6,7 +6,8 @@ LightGCN d = 64 on the bench.py C2 graph in the forms of the column sweep:
   wave         item rows by the wave form (§14), user rows by the row kernel
   wave+users   both blocks by the wave form
 
-and, with --sizes, the wave form at other (tile_rows, band_rows).  The forms
+and, with --sizes, the wave form at other (tile_rows, band_rows); with --pace,
+both blocks swept and one of them paced per XCD.  The forms
 alternate inside one process; each figure is the median of --reps device-event
 timings after --warmup launches.  Prints one JSON line per form.
 
@@ -33,6 +34,9 @@ def main():
     ap.add_argument("--edges", type=int, default=20_000_000)
     ap.add_argument("--sizes", default="",
                     help="comma list of block:TILExBAND, block = items or users")
+    ap.add_argument("--pace", default="",
+                    help="comma list of block:LEAD/EVERY/NAP (per-XCD pacing of that block)")
+    ap.add_argument("--forms", default="row,group,wave,wave+users")
     args = ap.parse_args()
     from furusato_recommend_amd import SyntheticBipartite
     from furusato_recommend_amd._lib import IN_PRESCALED
@@ -47,6 +51,8 @@ def main():
              "wave+users": {"sweep_form": "wave", "sweep_users": True}}
     engines = {}
     for name, sw in forms.items():
+        if name not in args.forms.split(","):
+            continue
         engines[name] = (PropagationEngine(g, D, 3, 2048), sw, None)
     for spec in filter(None, args.sizes.split(",")):
         block, size = spec.split(":")
@@ -54,6 +60,14 @@ def main():
         eng = PropagationEngine(g, D, 3, 2048)
         sw = {"sweep_form": "wave", "sweep_users": block == "users"}
         engines[spec] = (eng, sw, {"wave_" + block: (tile, band)})
+    # paced rows: both blocks swept, one block paced
+    for spec in filter(None, args.pace.split(",")):
+        block, v = spec.split(":")
+        pace = {"items": None, "users": None}
+        pace[block] = tuple(int(t) for t in v.split("/"))
+        eng = PropagationEngine(g, D, 3, 2048)
+        engines["pace " + spec] = (eng, {"sweep_form": "wave", "sweep_users": True,
+                                         "sweep_pace": pace}, None)
     for name, (eng, sw, sizes) in engines.items():
         for k, v in sw.items():
             setattr(eng, k, v)

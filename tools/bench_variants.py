@@ -30,7 +30,22 @@ VARIANTS = {
     "sweep_group": {"sweep_form": "group", "sweep_users": False},
     "sweep_wave": {"sweep_form": "wave", "sweep_users": False},
     "sweep_wave_users": {"sweep_form": "wave", "sweep_users": True},
+    # per-XCD pacing of the swept launches and the layer sum of a pruned
+    # forward on S only; --pace sets sweep_pace_on's parameters
+    "sweep_pace_off": {"sweep_pace": None},
+    "sweep_pace_on": {"sweep_pace": {"items": (8, 16, 16), "users": (4, 4, 16)}},
+    "layer_sum_hop": {"layer_sum_rows": "hop"},
+    "layer_sum_self": {"layer_sum_rows": "self"},
 }
+
+
+def parse_pace(spec: str) -> dict:
+    """items:LEAD/EVERY/NAP,users:LEAD/EVERY/NAP (a block left out: unpaced)"""
+    pace = {"items": None, "users": None}
+    for part in filter(None, spec.split(",")):
+        block, v = part.split(":")
+        pace[block] = tuple(int(t) for t in v.split("/"))
+    return pace
 
 
 def main():
@@ -43,7 +58,10 @@ def main():
     ap.add_argument("--edges", type=int, default=20_000_000)
     ap.add_argument("--dim", type=int, default=64)
     ap.add_argument("--batch", type=int, default=2048)
+    ap.add_argument("--pace", default="", help="sweep_pace_on: items:LEAD/EVERY/NAP,users:...")
     args = ap.parse_args()
+    if args.pace:
+        VARIANTS["sweep_pace_on"] = {"sweep_pace": parse_pace(args.pace)}
     from furusato_recommend_amd import LightGCN, SyntheticBipartite
     from furusato_recommend_amd.engine import sample_triples
     dev = torch.device("cuda:0")
