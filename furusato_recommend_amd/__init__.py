@@ -13,10 +13,11 @@ from .graphsage import GraphSAGE  # noqa: F401
 from .lgconv import LGConv  # noqa: F401
 from . import ops  # noqa: F401  (registers torch.ops.mirec.*)
 from .lightgcn import LightGCN  # noqa: F401
+from .lgcnssm import LightGCNSSM  # noqa: F401
 from .mf import MF  # noqa: F401
 from .radj import rAdjGCN  # noqa: F401
 from .sasrec import SASRec  # noqa: F401
 from .register import MODELS  # noqa: F401
 
-__all__ = ["LGConv", "LightGCN", "rAdjGCN", "MF", "GraphSAGE", "SASRec", "Graph", "Loader", "SyntheticBipartite", "FiveCore", "MODELS",
+__all__ = ["LGConv", "LightGCN", "LightGCNSSM", "rAdjGCN", "MF", "GraphSAGE", "SASRec", "Graph", "Loader", "SyntheticBipartite", "FiveCore", "MODELS",
            "MirecError", "LIB_PATH"]

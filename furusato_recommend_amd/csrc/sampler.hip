@@ -148,6 +148,65 @@ __global__ __launch_bounds__(256) void bpr_sample_kernel(
     err[0] = 1;
 }
 
+// Pair t of a sampled-softmax call: bpr_sample_one's stream (the same user,
+// positive and first negative), continued for negatives 1 .. n_neg - 1, each
+// uniform over [0, m_items) and rejected while it is a positive of u (with
+// replacement among themselves).  neg is [batch, n_neg] row-major; false if
+// a draw exhausted its retry budget.
+__host__ __device__ __forceinline__ bool ssm_sample_one(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+    const int32_t *__restrict__ sorted, const double *__restrict__ pos_cdf, int64_t n_users,
+    int64_t m_items, int32_t n_neg, int64_t t, uint64_t seed, uint64_t offset, int32_t shard,
+    int32_t n_shards, int32_t *users, int32_t *pos, int32_t *neg) {
+  XorShift64Star rng;
+  const uint64_t key = splitmix64(seed + 0xD1B54A32D192ED03ull * (uint64_t)shard);
+  rng.s = splitmix64(key ^ (offset + (uint64_t)t));
+  if (rng.s == 0) rng.s = 0x853C49E6748FEA9Bull;
+  const int64_t n_local = (n_users - shard + n_shards - 1) / n_shards;
+  int64_t u = 0, beg = 0, deg = 0;
+  int tries = 0;
+  do {
+    u = shard + (int64_t)n_shards * rng.below(n_local);
+    beg = rowptr[u];
+    deg = rowptr[u + 1] - beg;
+  } while (deg == 0 && ++tries < kMaxUserTries);
+  int32_t *ng = neg + t * n_neg;
+  if (deg == 0) {
+    users[t] = (int32_t)u;
+    pos[t] = 0;
+    for (int32_t k = 0; k < n_neg; ++k) ng[k] = 0;
+    return false;
+  }
+  const int64_t base = rowptr[0];
+  const int64_t p = (int64_t)col[beg + draw_positive(rng, pos_cdf, base, beg, deg)] - n_users;
+  bool all_ok = true;
+  for (int32_t k = 0; k < n_neg; ++k) {
+    int64_t n = 0;
+    bool ok = false;
+    for (int i = 0; i < kMaxNegTries && !ok; ++i) {
+      n = rng.below(m_items);
+      ok = !row_has(col, sorted, base, beg, deg, (int32_t)(n_users + n));
+    }
+    ng[k] = (int32_t)n;
+    all_ok = all_ok && ok;
+  }
+  users[t] = (int32_t)u;
+  pos[t] = (int32_t)p;
+  return all_ok;
+}
+
+__global__ __launch_bounds__(256) void ssm_sample_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+    const int32_t *__restrict__ sorted, const double *__restrict__ pos_cdf, int64_t n_users,
+    int64_t m_items, int64_t batch, int32_t n_neg, uint64_t seed, uint64_t offset, int32_t shard,
+    int32_t n_shards, int32_t *users, int32_t *pos, int32_t *neg, int32_t *err) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= batch) return;
+  if (!ssm_sample_one(rowptr, col, sorted, pos_cdf, n_users, m_items, n_neg, t, seed, offset,
+                      shard, n_shards, users, pos, neg))
+    err[0] = 1;
+}
+
 // ---------------------------------------------------------------------------
 // The ddp_lgcn.py epoch sampler (ddp_lgcn.py:33-35, 541-582): n_cand =
 // TRAIN_ITERATIVE x trainDataSize candidate users drawn uniformly (users
@@ -406,6 +465,57 @@ extern "C" int mirec_bpr_sample(const mirec_csr_t *csr, int64_t n_users, int64_t
                                 int32_t *err, mirec_stream_t stream) {
   return mirec_bpr_sample_ex(csr, nullptr, n_users, m_items, batch, seed, offset, shard, n_shards,
                              users, pos, neg, err, stream);
+}
+
+extern "C" int mirec_ssm_sample(const mirec_csr_t *csr, const double *pos_cdf, int64_t n_users,
+                                int64_t m_items, int64_t batch, int32_t n_neg, uint64_t seed,
+                                uint64_t offset, int32_t shard, int32_t n_shards, int32_t *users,
+                                int32_t *pos, int32_t *neg, int32_t *err, mirec_stream_t stream) {
+  using namespace mirec;
+  MIREC_CHECK_ARG(csr && csr->rowptr && csr->col && users && pos && neg && err);
+  MIREC_CHECK_ARG(n_users > 0 && m_items > 0 && batch >= 0 && n_neg >= 1);
+  MIREC_CHECK_ARG(n_shards >= 1 && shard >= 0 && shard < n_shards && shard < n_users);
+  MIREC_CHECK_ARG(csr->n_rows >= n_users + m_items);
+  if (batch == 0) return MIREC_OK;
+  hipLaunchKernelGGL(ssm_sample_kernel, dim3((batch + 255) / 256), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), csr->rowptr, csr->col,
+                     csr->n_sorted >= n_users ? csr->col_sorted : nullptr, pos_cdf, n_users,
+                     m_items, batch, n_neg, seed, offset, shard, n_shards, users, pos, neg, err);
+  MIREC_LAUNCH_CHECK();
+  return MIREC_OK;
+}
+
+// mirec_ssm_sample on the host: the same streams on CPU threads (contiguous
+// blocks of pairs), the device sampler's output bit for bit.
+extern "C" int mirec_cpu_ssm_sample(const int64_t *rowptr, const int32_t *col,
+                                    const int32_t *col_sorted, const double *pos_cdf,
+                                    int64_t n_users, int64_t m_items, int64_t batch,
+                                    int32_t n_neg, uint64_t seed, uint64_t offset, int32_t shard,
+                                    int32_t n_shards, int32_t *users, int32_t *pos, int32_t *neg,
+                                    int32_t *err, int32_t n_threads) {
+  using namespace mirec;
+  MIREC_CHECK_ARG(rowptr && col && users && pos && neg && err);
+  MIREC_CHECK_ARG(n_users > 0 && m_items > 0 && batch >= 0 && n_neg >= 1);
+  MIREC_CHECK_ARG(n_shards >= 1 && shard >= 0 && shard < n_shards && shard < n_users);
+  if (batch == 0) return MIREC_OK;
+  const int nt = (int)std::max<int64_t>(
+      1, std::min<int64_t>(std::min<int64_t>(n_threads > 0 ? n_threads : 1, 64),
+                           (batch + 4095) / 4096));
+  std::vector<int> bad(nt, 0);
+  auto work = [&](int w) {
+    const int64_t a = batch * w / nt, b = batch * (w + 1) / nt;
+    for (int64_t t = a; t < b; ++t)
+      if (!ssm_sample_one(rowptr, col, col_sorted, pos_cdf, n_users, m_items, n_neg, t, seed,
+                          offset, shard, n_shards, users, pos, neg))
+        bad[w] = 1;
+  };
+  std::vector<std::thread> th;
+  for (int w = 1; w < nt; ++w) th.emplace_back(work, w);
+  work(0);
+  for (auto &x : th) x.join();
+  for (int w = 0; w < nt; ++w)
+    if (bad[w]) err[0] = 1;
+  return MIREC_OK;
 }
 
 // The same sampler on the host (configuration C1, "CPU single-process":

@@ -102,6 +102,12 @@ class DataParallel:
             # the seed exchange and the sharded update; not verified yet
             raise NotImplementedError("data-parallel training with edge dropout "
                                       "(config['dropout']) is not implemented")
+        if getattr(engine, "n_neg", 1) > 1 or getattr(engine, "loss_name", "bpr") == "ssm":
+            # the seed exchange is n-generic, but nobody has verified it on
+            # (2 + K) B seeds per rank
+            raise NotImplementedError("data-parallel training with the sampled-softmax loss "
+                                      "(config['loss'] = 'ssm', neg_size > 1) is not "
+                                      "implemented")
         self.requested = mode
         self.mode = "sparse" if mode == "auto" else mode
         self.engine = engine

@@ -29,6 +29,10 @@ launches with no host synchronisation:
                           dinv ⊙ E_new, the next step's x~_0.
   reset    (1)            slot[] back to -1 for the touched nodes.
 
+``train_step_ssm`` is the same step with the sampled-softmax loss (K
+negatives per positive, csrc/ssm.hip) in the BPR stage's place
+and the frontier taken from the batch's (2 + K) B node keys.
+
 For data parallelism (dist.py) the ranks exchange their gradient seeds
 before the backward (sparse mode), or the last layer writes the dense
 gradient and the caller all-reduces it before ``adam_step`` (dense mode).
@@ -263,7 +267,9 @@ class PropagationEngine:
     fp32 summation order; ``prune=False`` runs every layer on every row."""
 
     def __init__(self, graph: Graph, dim: int, n_layers: int, max_batch: int,
-                 prune: bool = True):
+                 prune: bool = True, n_neg: int = 1):
+        if int(n_neg) < 1:
+            raise ValueError(f"n_neg must be at least 1, got {n_neg!r}")
         if dim not in _lib.SUPPORTED_DIMS:
             raise ValueError(f"recdim={dim} not supported by the HIP engine "
                              f"(supported: {_lib.SUPPORTED_DIMS})")
@@ -274,6 +280,12 @@ class PropagationEngine:
         self.L = int(n_layers)
         self.max_batch = int(max_batch)
         self.prune = bool(prune)
+        # negatives per positive of the sampled-softmax loss (ssm); a batch
+        # has up to (2 + n_neg) * max_batch seed keys (BPR: n_neg = 1, 3B)
+        self.n_neg = int(n_neg)
+        # the owner's loss, "bpr" or "ssm" (the data-parallel wrappers refuse
+        # "ssm" and n_neg > 1: their seed exchange is not verified for it)
+        self.loss_name = "bpr"
         dev = graph.device
         N, D = graph.n_nodes, self.dim
         f32 = dict(dtype=torch.float32, device=dev)
@@ -287,7 +299,8 @@ class PropagationEngine:
         # S and S ∪ N(S) byte maps (int32-backed), adjacent: cleared together
         self._bm = torch.zeros(2, words, **i32)
         self.bm_self, self.bm_hop = self._bm[0], self._bm[1]
-        self.self_list = torch.zeros(3 * self.max_batch, **i32)  # S, deduplicated
+        # S, deduplicated
+        self.self_list = torch.zeros((2 + self.n_neg) * self.max_batch, **i32)
         self.self_count = torch.zeros(1, **i32)
         self._self_cap = 0
         # S and F1 as row lists split by degree (narrow: <= narrow_max,
@@ -328,10 +341,11 @@ class PropagationEngine:
         self._masks_ready = False
         # rows of degree <= narrow_max are gathered one per lane group
         self.narrow_max = 64
-        B3 = 3 * self.max_batch
+        B3 = (2 + self.n_neg) * self.max_batch
         self.seed_p = torch.empty(B3, D, **f32)
         self.seed_e = torch.empty(B3, D, **f32)
-        self.coef = torch.empty(self.max_batch, **f32)
+        self.coef = torch.empty(self.n_neg * self.max_batch, **f32)
+        self.coef_pos = self.g_u = None  # ssm()'s own buffers, made on first use
         self.softplus = torch.empty(self.max_batch, **f32)
         self.reg = torch.empty(self.max_batch, **f32)
         self.keys = torch.empty(B3, **i32)
@@ -396,6 +410,18 @@ class PropagationEngine:
         nb = ctypes.c_size_t(0)
         check(lib.mirec_bpr_seed_workspace(batch, self.g.n_nodes, ctypes.byref(nb)),
               "bpr_seed_workspace")
+        if nb.value > self._ws_bytes:
+            self._ws = torch.empty(nb.value, dtype=torch.uint8, device=self.g.device)
+            self._ws_bytes = nb.value
+
+    def _ensure_ssm(self, batch: int, n_neg: int):
+        if self.g_u is None:
+            f32 = dict(dtype=torch.float32, device=self.g.device)
+            self.coef_pos = torch.empty(self.max_batch, **f32)
+            self.g_u = torch.empty(self.max_batch, self.dim, **f32)
+        nb = ctypes.c_size_t(0)
+        check(lib.mirec_ssm_seed_workspace(batch, n_neg, self.g.n_nodes, ctypes.byref(nb)),
+              "ssm_seed_workspace")
         if nb.value > self._ws_bytes:
             self._ws = torch.empty(nb.value, dtype=torch.uint8, device=self.g.device)
             self._ws_bytes = nb.value
@@ -671,7 +697,7 @@ class PropagationEngine:
     def _sparse_filter(self):
         f = self.sparse_filter
         if f == "auto":
-            f = "bytemap" if self._self_cap > 3 * self.max_batch else "slot"
+            f = "bytemap" if self._self_cap > (2 + self.n_neg) * self.max_batch else "slot"
         return self.bm_self if f == "bytemap" else None
 
     def static_row_lists(self, bm: torch.Tensor) -> dict:
@@ -834,6 +860,66 @@ class PropagationEngine:
         self._seeds = (self.seed_p, self.seed_e, self.keys_sorted, 3 * B)
         return self.loss
 
+    # -------------------------------------------------------- sampled softmax
+    def _ssm_shape(self, users, neg):
+        """(B, K) of an SSM batch: int32 ``neg`` of shape [B, K], K <= n_neg."""
+        B = int(users.shape[0])
+        if B > self.max_batch:
+            raise ValueError(f"batch {B} > engine max_batch {self.max_batch}")
+        if neg.dim() != 2 or int(neg.shape[0]) != B or int(neg.shape[1]) < 1:
+            raise ValueError(f"ssm: neg must have shape [{B}, K], got {tuple(neg.shape)}")
+        K = int(neg.shape[1])
+        if K > self.n_neg:
+            raise ValueError(f"ssm: {K} negatives per pair > engine n_neg {self.n_neg}")
+        if neg.dtype != torch.int32 or not neg.is_contiguous():
+            raise ValueError("ssm: neg must be a contiguous int32 tensor")
+        return B, K
+
+    def frontier_ssm(self, users, pos, neg):
+        """compute_frontier of an SSM batch: its (2 + K) B node ids are written
+        on the device (mirec_ssm_keys) and given to the key-list frontier."""
+        B, K = self._ssm_shape(users, neg)
+        check(lib.mirec_ssm_keys(users.data_ptr(), pos.data_ptr(), neg.data_ptr(), B, K,
+                                 self.g.n_users, self.keys.data_ptr(), _lib.stream_handle()),
+              "ssm_keys")
+        self.compute_frontier(keys=self.keys, n_keys=(2 + K) * B)
+
+    def ssm(self, out: torch.Tensor, emb: torch.Tensor, users, pos, neg, decay: float,
+            temp: float, loss_accum: torch.Tensor | None = None,
+            grad_scale: float = 1.0) -> torch.Tensor:
+        """Sampled-softmax loss + gradient seeds for one batch: int32 device
+        ``users`` / ``pos`` [B] and ``neg`` [B, K] (K <= n_neg), temperature
+        ``temp``: loss = mean_t (logsumexp(s+_t, s_t,.) - s+_t) + decay *
+        sum_t reg_t / B (K = 1, temp = 1 is bpr())."""
+        B, K = self._ssm_shape(users, neg)
+        if not (float(temp) > 0.0 and math.isfinite(float(temp))):
+            raise ValueError(f"ssm: temp must be positive and finite, got {temp!r}")
+        if not self._masks_ready:
+            self.frontier_ssm(users, pos, neg)  # the seed set S for the backward
+        self._ensure_ssm(B, K)
+        st = _lib.stream_handle()
+        g = self.g
+        check(lib.mirec_ssm_forward(out.data_ptr(), emb.data_ptr(), g.n_nodes, g.n_users,
+                                    self.dim, B, K, users.data_ptr(), pos.data_ptr(),
+                                    neg.data_ptr(), float(temp), float(grad_scale),
+                                    self.coef.data_ptr(), self.coef_pos.data_ptr(),
+                                    self.softplus.data_ptr(), self.reg.data_ptr(),
+                                    self.g_u.data_ptr(), self.keys.data_ptr(),
+                                    self.vals.data_ptr(), st), "ssm_forward")
+        check(lib.mirec_bpr_loss(self.softplus.data_ptr(), self.reg.data_ptr(), B,
+                                 float(decay), self.loss.data_ptr(), ptr(loss_accum), st),
+              "bpr_loss")
+        check(lib.mirec_ssm_seed(out.data_ptr(), emb.data_ptr(), g.n_nodes, g.n_users, self.dim,
+                                 B, K, users.data_ptr(), self.coef.data_ptr(),
+                                 self.coef_pos.data_ptr(), self.g_u.data_ptr(),
+                                 self.keys.data_ptr(), self.vals.data_ptr(), float(decay),
+                                 float(grad_scale), self.L, self.slot.data_ptr(),
+                                 self.seed_p.data_ptr(), self.seed_e.data_ptr(),
+                                 self.keys_sorted.data_ptr(), self._ws.data_ptr(),
+                                 self._ws_bytes, st), "ssm_seed")
+        self._seeds = (self.seed_p, self.seed_e, self.keys_sorted, (2 + K) * B)
+        return self.loss
+
     # ----------------------------------------------- data-parallel exchange
     def export_seeds(self):
         """Local seeds as fixed-size rows for an all-gather: (keys [3B] int32,
@@ -978,6 +1064,24 @@ class PropagationEngine:
             self.set_dropout(None)
         return loss
 
+    def train_step_ssm(self, emb: torch.Tensor, adam: AdamState, users, pos, neg, decay: float,
+                       temp: float, loss_accum: torch.Tensor | None = None,
+                       dropout=None) -> torch.Tensor:
+        """train_step with the sampled-softmax loss: frontier of the batch's
+        (2 + K) B nodes, (pruned) forward, ssm(), backward, fused Adam; no
+        host synchronisation.  ``neg`` is [B, K]; ``dropout`` as train_step's."""
+        if dropout is not None:
+            self.set_dropout(*dropout)
+        try:
+            self.frontier_ssm(users, pos, neg)
+            out = self.forward(emb, pruned=self.prune)
+            loss = self.ssm(out, emb, users, pos, neg, decay, temp, loss_accum)
+            self.backward(emb, adam=adam)
+        finally:
+            if dropout is not None:
+                self.set_dropout(None)
+        return loss
+
 
 def edge_dot(graph: Graph, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor):
     """out[k] = <a[row(k)], b[col[k]]> for every CSR entry k of ``graph``
@@ -1045,6 +1149,20 @@ def sample_triples(graph: Graph, batch: int, seed: int, offset: int, users, pos,
                                   int(n_shards), users.data_ptr(), pos.data_ptr(),
                                   neg.data_ptr(), err.data_ptr(), _lib.stream_handle()),
           "bpr_sample")
+
+
+def sample_pairs(graph: Graph, batch: int, n_neg: int, seed: int, offset: int, users, pos, neg,
+                 err, shard: int = 0, n_shards: int = 1):
+    """sample_triples with ``n_neg`` negatives per pair (mirec_ssm_sample):
+    int32 ``neg`` of shape [batch, n_neg]; the user, positive and first
+    negative of pair t are sample_triples' of the same (seed, offset)."""
+    check(lib.mirec_ssm_sample(graph.csr_ptr(), ptr(getattr(graph, "pos_cdf", None)),
+                               graph.n_users, graph.m_items, int(batch), int(n_neg),
+                               ctypes.c_uint64(seed & (2**64 - 1)),
+                               ctypes.c_uint64(offset & (2**64 - 1)), int(shard),
+                               int(n_shards), users.data_ptr(), pos.data_ptr(),
+                               neg.data_ptr(), err.data_ptr(), _lib.stream_handle()),
+          "ssm_sample")
 
 
 def sample_epoch_capped(graph: Graph, n_candidates: int, cap: int, seed: int, offset: int = 0,

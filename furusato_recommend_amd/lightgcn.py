@@ -14,6 +14,13 @@ Two execution paths, both on libmirec:
     autograd.Function whose backward is the same HIP SpMM (Â is symmetric),
     for callers that build their own loss.
 
+``config["loss"] = "ssm"`` trains with the sampled-softmax loss instead of
+BPR: ``config["neg_size"]`` negatives per positive and the temperature
+``config["ssm_temp"]`` (engine.PropagationEngine.train_step_ssm, DESIGN.md
+§18); ``stageOne`` / ``OneEpoch`` / ``sample`` then carry ``neg`` of shape
+[n, neg_size], and ``softmax_loss`` is the differentiable form.
+``LightGCNSSM`` (lgcnssm.py, 'lgnssm') is this class with that default.
+
 ``rAdjGCN`` (radj.py) is this class on a graph with the r-adjusted
 normalisation; ``LightGCN`` itself ignores ``config["r"]``, as the
 reference's 'lgn' does (model/lgcn.py never reads it).
@@ -23,7 +30,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .engine import AdamState, PropagationEngine, sample_triples
+from .engine import AdamState, PropagationEngine, sample_pairs, sample_triples
 from .graph import DEFAULT_SPLIT, Graph, positive_probs
 
 
@@ -77,6 +84,7 @@ class LightGCN(nn.Module):
     sides; ``rAdjGCN`` is the model that reads it."""
 
     edge_dropout_supported = True  # config["dropout"]; rAdjGCN refuses it
+    default_loss = "bpr"           # config["loss"] when absent; LightGCNSSM: "ssm"
 
     def _graph_r(self, config) -> float:
         """The r of the graph's normalisation 1 / (deg_j^r · deg_i^(1−r))."""
@@ -122,6 +130,24 @@ class LightGCN(nn.Module):
             if not self.edge_dropout_supported:
                 raise ValueError(f"config['dropout'] with {type(self).__name__}: edge dropout "
                                  "and the r-adjusted normalisation's scales are not combined")
+        # config["loss"]: "bpr" (one negative per positive, model/lgcn.py:98-118)
+        # or "ssm", the sampled softmax over config["neg_size"] negatives per
+        # positive at temperature config["ssm_temp"] (the intent of
+        # model/lgcnssm.py, whose neg_size is undefined and whose loss body is
+        # still the BPR softplus; DESIGN.md §18 has the definition).
+        self.loss_name = str(_config_get(config, "loss", default=self.default_loss))
+        if self.loss_name not in ("bpr", "ssm"):
+            raise ValueError(f"config['loss'] must be 'bpr' or 'ssm', got {self.loss_name!r}")
+        neg_size = _config_get(config, "neg_size", default=1)
+        if int(neg_size) != neg_size or int(neg_size) < 1:
+            raise ValueError(f"config['neg_size'] must be an integer >= 1, got {neg_size!r}")
+        self.neg_size = int(neg_size)
+        self.ssm_temp = float(_config_get(config, "ssm_temp", default=1.0))
+        if not (self.ssm_temp > 0.0 and self.ssm_temp < float("inf")):
+            raise ValueError(f"config['ssm_temp'] must be positive and finite, "
+                             f"got {self.ssm_temp!r}")
+        if self.loss_name == "bpr":
+            self.neg_size = 1  # the BPR loss takes one negative: the key is not read
         self.graph = Graph.from_interactions(dataset.trainUser, dataset.trainItem,
                                              self.num_users, self.num_items, self.device,
                                              split=int(config.get("csr_split", DEFAULT_SPLIT)),
@@ -131,7 +157,9 @@ class LightGCN(nn.Module):
         self.optim = AdamState(self.all_embedding.weight, lr=config["lr"])
         self.engine = PropagationEngine(self.graph, self.latent_dim, self.num_layers,
                                         int(config.get("bpr_batch_size", 2048)),
-                                        prune=bool(config.get("prune", True)))
+                                        prune=bool(config.get("prune", True)),
+                                        n_neg=self.neg_size)
+        self.engine.loss_name = self.loss_name
         self.engine.edge_dropout = self.keep_prob if self.dropout else None
         self._loss_accum = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.test_item_emb = None
@@ -186,6 +214,39 @@ class LightGCN(nn.Module):
         loss = torch.mean(torch.nn.functional.softplus(neg_scores - pos_scores))
         return loss, reg_loss
 
+    def softmax_loss(self, users, pos, neg):
+        """The sampled-softmax loss on ``forward()``, differentiable: ``neg``
+        is [n, K]; returns (mean_t logsumexp(s+_t, s_t,.) - s+_t, reg_loss)
+        with s = <u, i> / ssm_temp and reg_loss = 1/2 (|E_u|^2 + |E_p|^2 +
+        |E_neg|^2) / n over the gathered ego rows (a negative drawn twice
+        counts twice), as ``bpr_loss`` returns its pair.  What
+        model/lgcnssm.py:98-118 evidently means: its body is still the BPR
+        softplus, which this equals for K = 1, ssm_temp = 1."""
+        users, pos, neg = users.long(), pos.long(), self._neg2d(neg, len(users)).long()
+        all_users, all_items = self.forward()
+        ue, pe, ne = all_users[users], all_items[pos], all_items[neg]
+        u0 = self.all_embedding(users)
+        p0 = self.all_embedding(pos + self.num_users)
+        n0 = self.all_embedding(neg + self.num_users)
+        reg_loss = (0.5 * (u0.norm(2).pow(2) + p0.norm(2).pow(2) + n0.norm(2).pow(2))
+                    / float(len(users)))
+        sp = torch.sum(ue * pe, dim=1) / self.ssm_temp
+        sn = torch.einsum("bd,bkd->bk", ue, ne) / self.ssm_temp
+        lse = torch.logsumexp(torch.cat([sp[:, None], sn], dim=1), dim=1)
+        return torch.mean(lse - sp), reg_loss
+
+    def _neg2d(self, neg, n: int):
+        """``neg`` as the [n, K] tensor of the sampled-softmax paths
+        (K = neg_size; a flat [n] tensor is accepted for K = 1)."""
+        if not torch.is_tensor(neg):
+            neg = torch.as_tensor(neg)
+        if neg.dim() == 1 and self.neg_size == 1:
+            neg = neg[:, None]
+        if neg.dim() != 2 or tuple(neg.shape) != (n, self.neg_size):
+            raise ValueError(f"neg must have shape [{n}, {self.neg_size}] with "
+                             f"config['loss'] = 'ssm', got {tuple(neg.shape)}")
+        return neg
+
     @torch.no_grad()
     def propagated(self) -> torch.Tensor:
         """Full layer-mean embeddings [N, D] (no autograd; the engine's
@@ -226,18 +287,41 @@ class LightGCN(nn.Module):
 
     @torch.no_grad()
     def stageOne(self, user, pos, neg, loss_accum=None):
-        """One fused BPR step (model/lgcn.py:127-133); returns the loss tensor."""
+        """One fused BPR step (model/lgcn.py:127-133); returns the loss tensor.
+        With config["loss"] = "ssm": one sampled-softmax step, ``neg`` [n, K]."""
         w = self.all_embedding.weight
+        if self.loss_name == "ssm":
+            neg = self._as_i32(self._neg2d(neg, len(user)))
+            return self.engine.train_step_ssm(w, self.optim, self._as_i32(user),
+                                              self._as_i32(pos), neg,
+                                              float(self.config["decay"]), self.ssm_temp,
+                                              loss_accum, dropout=self._next_dropout()).clone()
         return self.engine.train_step(w, self.optim, self._as_i32(user), self._as_i32(pos),
                                       self._as_i32(neg), float(self.config["decay"]),
                                       loss_accum, dropout=self._next_dropout()).clone()
 
     @torch.no_grad()
     def OneEpoch(self, user, pos, neg):
-        """model/lgcn.py:135-151: minibatch loop; mean loss over len//B + 1."""
+        """model/lgcn.py:135-151: minibatch loop; mean loss over len//B + 1.
+
+        With config["loss"] = "ssm" a batch is ``bpr_batch_size`` pairs, each
+        with its K negatives (``neg`` [n, K]).  model/lgcnssm.py:135-151
+        slices ``neg_size * bpr_batch_size`` rows of flat triples instead,
+        which cannot be followed: its own sampler never produces such
+        triples (and ``neg_size`` is undefined there)."""
         B = int(self.config["bpr_batch_size"])
         n = len(user)
         total_batch = n // B + 1
+        if self.loss_name == "ssm":
+            user, pos = self._as_i32(user), self._as_i32(pos)
+            neg = self._as_i32(self._neg2d(neg, n))
+            self._loss_accum.zero_()
+            for i in range(0, n, B):
+                self.engine.train_step_ssm(self.all_embedding.weight, self.optim, user[i:i + B],
+                                           pos[i:i + B], neg[i:i + B],
+                                           float(self.config["decay"]), self.ssm_temp,
+                                           self._loss_accum, dropout=self._next_dropout())
+            return self._loss_accum[0] / total_batch
         user, pos, neg = self._as_i32(user), self._as_i32(pos), self._as_i32(neg)
         self._loss_accum.zero_()
         for i in range(0, n, B):
@@ -249,10 +333,19 @@ class LightGCN(nn.Module):
     # ------------------------------------------------------------- sampling
     def sample(self, n_triples: int, seed: int, offset: int = 0, shard: int = 0,
                n_shards: int = 1):
-        """On-device UniformSample: int32 (users, pos, neg) device tensors."""
+        """On-device UniformSample: int32 (users, pos, neg) device tensors;
+        with config["loss"] = "ssm" ``neg`` is [n_triples, neg_size]
+        (mirec_ssm_sample: the same users, positives and first negatives)."""
         dev = self.device
         u = torch.empty(n_triples, dtype=torch.int32, device=dev)
         p = torch.empty_like(u)
+        if self.loss_name == "ssm":
+            n = torch.empty(n_triples, self.neg_size, dtype=torch.int32, device=dev)
+            err = torch.zeros(1, dtype=torch.int32, device=dev)
+            sample_pairs(self.graph, n_triples, self.neg_size, seed, offset, u, p, n, err,
+                         shard, n_shards)
+            self._sample_err = err
+            return u, p, n
         n = torch.empty_like(u)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
         sample_triples(self.graph, n_triples, seed, offset, u, p, n, err, shard, n_shards)

@@ -1,7 +1,8 @@
 """Model registry with the reference's names (main.py:32-56, subset on the
-hot path: 'lgn' = LightGCN, 'radj' = rAdjGCN, 'mf' = MF, 'sage' = GraphSAGE,
-'sasrec' = SASRec)."""
+hot path: 'lgn' = LightGCN, 'lgnssm' = LightGCNSSM, 'radj' = rAdjGCN,
+'mf' = MF, 'sage' = GraphSAGE, 'sasrec' = SASRec)."""
 from .graphsage import GraphSAGE
+from .lgcnssm import LightGCNSSM
 from .lightgcn import LightGCN
 from .mf import MF
 from .radj import rAdjGCN
@@ -10,6 +11,7 @@ from .sasrec import SASRec
 MODELS = {
     "mf": MF,
     "lgn": LightGCN,
+    "lgnssm": LightGCNSSM,
     "radj": rAdjGCN,
     "sage": GraphSAGE,
     "sasrec": SASRec,

@@ -101,6 +101,9 @@ def wrap(model, group=None, mode: str | None = None, **kw):
     if getattr(model, "dropout", False) is True and hasattr(model, "all_embedding"):
         raise NotImplementedError("data-parallel training of a LightGCN with edge dropout "
                                   "(config['dropout']) is not implemented")
+    if getattr(model, "loss_name", "bpr") == "ssm":
+        raise NotImplementedError("data-parallel training with the sampled-softmax loss "
+                                  "(config['loss'] = 'ssm') is not implemented")
     if hasattr(model, "engine") and hasattr(model, "all_embedding"):
         return DataParallel(model.engine, model.all_embedding.weight.data, model.optim,
                             group=group, mode=mode or "auto", **kw)

@@ -34,9 +34,19 @@ class Trainer:
         self.epoch = 0
         self.max_recall = 0.0
         self.history = []
+        self._check_sampler()
+
+    def _check_sampler(self):
+        """The capped epoch sampler draws one negative per kept candidate: it
+        has no form for the sampled-softmax loss's [n, K] negatives."""
+        if (self.config.get("sampler", "uniform") == "ddp_capped"
+                and getattr(self.model, "loss_name", "bpr") == "ssm"):
+            raise ValueError("config['sampler'] = 'ddp_capped' with config['loss'] = 'ssm': "
+                             "the capped sampler draws one negative per triple")
 
     def train(self):
         n = int(self.dataset.trainDataSize)
+        self._check_sampler()
         if self.config.get("sampler", "uniform") == "ddp_capped":
             from .engine import sample_epoch_capped
             nc = int(self.config.get("train_iterative", 3)) * n

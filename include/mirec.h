@@ -698,6 +698,61 @@ int mirec_seed_merge(const int32_t *keys_packed, const float *rows_p,
                      size_t workspace_bytes, mirec_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* Sampled softmax: K = n_neg negatives per positive (csrc/ssm.hip; the      */
+/* intent of model/lgcnssm.py's softmax_loss; K = 1, temp = 1 is BPR)        */
+/* ------------------------------------------------------------------------ */
+
+/* Pair t = (users[t], pos[t]) has the negatives neg[t * n_neg + k] (item
+ * ids without the n_users offset), temp > 0 is the temperature.  With
+ * s+ = <out_u, out_p> / temp and s_k = <out_u, out_nk> / temp:
+ *   terms[t]     = logsumexp(s+, s_0 .. s_{K-1}) - s+   (max-subtracted)
+ *   reg[t]       = 1/2 (|e_u|^2 + |e_p|^2 + sum_k |e_nk|^2)  (a negative
+ *                  drawn twice counts twice)
+ *   coef[t*K+k]  = grad_scale * softmax weight of negative k / (B temp)
+ *   coef_pos[t]  = sum_k coef[t*K+k]
+ *   g_u[t, :]    = sum_k coef[t*K+k] out_nk - coef_pos[t] out_p  (the user
+ *                  row's gradient, summed k = 0 .. K-1, then the positive)
+ * and the (2 + K) B seed keys / values (node id, occurrence index) of
+ * mirec_ssm_seed: occurrence t is the user of pair t, B + t its positive,
+ * 2B + t K + k its negative k.  The loss is mirec_bpr_loss(terms, reg).
+ * MIREC_ERR_ARG: a NULL pointer, batch < 1, n_neg < 1, temp <= 0 or not
+ * finite, an unsupported dim, (2 + K) B >= 2^31. */
+int mirec_ssm_forward(const float *out, const float *emb, int64_t n_nodes,
+                      int64_t n_users, int32_t dim, int64_t batch, int32_t n_neg,
+                      const int32_t *users, const int32_t *pos, const int32_t *neg,
+                      float temp, float grad_scale, float *coef, float *coef_pos,
+                      float *terms, float *reg, float *g_u, int32_t *keys,
+                      int32_t *vals, mirec_stream_t stream);
+
+/* The keys of mirec_ssm_forward alone (keys[(2 + K) B]: users, n_users +
+ * pos, n_users + neg): the batch's node list for mirec_frontier's key form,
+ * which a pruned forward needs before the scores exist. */
+int mirec_ssm_keys(const int32_t *users, const int32_t *pos, const int32_t *neg,
+                   int64_t batch, int32_t n_neg, int64_t n_users, int32_t *keys,
+                   mirec_stream_t stream);
+
+/* Scratch bytes mirec_ssm_seed needs. */
+int mirec_ssm_seed_workspace(int64_t batch, int32_t n_neg, int64_t n_nodes, size_t *bytes);
+
+/* Gradient seeds from mirec_ssm_forward's outputs, laid out as
+ * mirec_bpr_seed's: stable sort of the (2 + K) B pairs (the small sort up to
+ * 8 192 pairs, the radix sort above), slot[node] = q at the first position
+ * of every distinct node (slot all -1 on entry), and
+ *   seed_p[q] = (sum over the node's occurrences, in occurrence order, of
+ *                1 * g_u[t] | -coef_pos[t] * out_u | coef[t*K+k] * out_u
+ *                for a user | positive | negative occurrence) / (L+1)
+ *   seed_e[q] = decay * (#occurrences) * emb[node] / B * grad_scale
+ * keys_sorted[(2 + K) B] feeds mirec_bpr_seed_reset.  Deterministic: one
+ * fixed summation order, no float atomics. */
+int mirec_ssm_seed(const float *out, const float *emb, int64_t n_nodes, int64_t n_users,
+                   int32_t dim, int64_t batch, int32_t n_neg, const int32_t *users,
+                   const float *coef, const float *coef_pos, const float *g_u,
+                   const int32_t *keys, const int32_t *vals, float decay,
+                   float grad_scale, int32_t n_layers, int32_t *slot, float *seed_p,
+                   float *seed_e, int32_t *keys_sorted, void *workspace,
+                   size_t workspace_bytes, mirec_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* Adam (torch.optim.Adam, amsgrad=False, weight_decay=0)                   */
 /* ------------------------------------------------------------------------ */
 
@@ -787,6 +842,17 @@ int mirec_bpr_sample_capped_ex(const mirec_csr_t *csr, const double *pos_cdf, in
                                int32_t *users, int32_t *pos, int32_t *neg, int32_t *count,
                                int32_t *err, int32_t *cand_u, int32_t *cand_p, void *workspace,
                                size_t workspace_bytes, mirec_stream_t stream);
+
+/* mirec_bpr_sample_ex with n_neg >= 1 negatives per pair (sampled softmax):
+ * pair t draws from the same stream (seed, offset + t) the same user,
+ * positive and first negative, then continues it for negatives 1 .. n_neg-1,
+ * each uniform over [0, m_items) and rejected while it is a positive of u
+ * (with replacement among themselves).  neg is [batch, n_neg] row-major;
+ * with n_neg = 1 the output is mirec_bpr_sample_ex's bit for bit. */
+int mirec_ssm_sample(const mirec_csr_t *csr, const double *pos_cdf, int64_t n_users,
+                     int64_t m_items, int64_t batch, int32_t n_neg, uint64_t seed,
+                     uint64_t offset, int32_t shard, int32_t n_shards, int32_t *users,
+                     int32_t *pos, int32_t *neg, int32_t *err, mirec_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* GraphSAGE hop ops (model/graphsage.py:311-324, neighbor_sampling.py)      */
@@ -1323,6 +1389,14 @@ int mirec_cpu_bpr_sample(const int64_t *rowptr, const int32_t *col, const int32_
                          uint64_t seed, uint64_t offset, int32_t shard, int32_t n_shards,
                          int32_t *users, int32_t *pos, int32_t *neg, int32_t *err,
                          int32_t n_threads);
+
+/* mirec_ssm_sample on the host: the same streams, the same output bit for
+ * bit, whatever n_threads. */
+int mirec_cpu_ssm_sample(const int64_t *rowptr, const int32_t *col, const int32_t *col_sorted,
+                         const double *pos_cdf, int64_t n_users, int64_t m_items, int64_t batch,
+                         int32_t n_neg, uint64_t seed, uint64_t offset, int32_t shard,
+                         int32_t n_shards, int32_t *users, int32_t *pos, int32_t *neg,
+                         int32_t *err, int32_t n_threads);
 
 /* mirec_bpr_sample_capped_ex on the host (the ddp_lgcn.py epoch sampler for
  * a CPU model): the same candidate streams, so users / pos / neg (capacity
