@@ -226,6 +226,25 @@ SIGNATURES = {
     "mirec_cpu_ssm_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                      c_int64, c_int32, c_uint64, c_uint64, c_int32, c_int32,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int32]),
+    "mirec_ssm_shared_keys": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                      c_void_p, c_void_p]),
+    "mirec_ssm_shared_mask": (c_int, [POINTER(CSR), c_void_p, c_int64, c_void_p, c_void_p,
+                                      c_int64, c_int64, c_void_p, c_void_p]),
+    "mirec_ssm_shared_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int64,
+                                         c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                         c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mirec_ssm_shared_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float,
+                                      c_void_p, c_void_p, c_void_p]),
+    "mirec_ssm_shared_seed_workspace": (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "mirec_ssm_shared_seed": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int64,
+                                      c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_float, c_float, c_int32, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mirec_shared_sample": (c_int, [c_int64, c_int64, c_int64, c_uint64, c_uint64, c_void_p,
+                                    c_void_p]),
+    "mirec_cpu_shared_sample": (c_int, [c_int64, c_int64, c_int64, c_uint64, c_uint64, c_void_p,
+                                        c_int32]),
     "mirec_adam_multi": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  POINTER(AdamH), c_void_p]),
     "mirec_adam_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64,

@@ -614,3 +614,105 @@ extern "C" int mirec_cpu_bpr_sample_capped(const int64_t *rowptr, const int32_t 
     if (bad[w]) err[0] = 1;
   return MIREC_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Shared negative sets of the sampled-softmax loss (ssm_shared.hip, DESIGN.md
+// §19): n_sets sets of m item ids, each uniform over [0, m_items), with
+// replacement and without rejection (the loss masks a pair's own positives).
+// Element i = b * m + j draws once from the stream keyed by (seed, this
+// sampler's own tag, offset) at counter i, so that set b of a call does not
+// depend on n_sets, the launch shape or the thread count, and calls with
+// different offsets are independent (not windows of one sequence).
+namespace mirec {
+
+__host__ __device__ __forceinline__ int32_t shared_sample_one(int64_t m_items, uint64_t seed,
+                                                              uint64_t offset, uint64_t i) {
+  const uint64_t key = splitmix64(splitmix64(seed ^ 0x6E65675F73686172ull) ^ offset);
+  XorShift64Star rng;
+  rng.s = splitmix64(key + i);
+  if (rng.s == 0) rng.s = 0x853C49E6748FEA9Bull;
+  return (int32_t)rng.below(m_items);
+}
+
+__global__ __launch_bounds__(256) void shared_sample_kernel(int64_t m_items, int64_t total,
+                                                            uint64_t seed, uint64_t offset,
+                                                            int32_t *out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  out[i] = shared_sample_one(m_items, seed, offset, (uint64_t)i);
+}
+
+// mask[t, j] = shared[j] is an entry of user t's row, or shared[j] == pos[t]
+__global__ __launch_bounds__(256) void ssm_shared_mask_kernel(
+    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+    const int32_t *__restrict__ sorted, const int32_t *__restrict__ users, int64_t batch,
+    const int32_t *__restrict__ pos, const int32_t *__restrict__ shared, int64_t m,
+    int32_t n_users, uint8_t *mask) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch * m) return;
+  const int64_t t = i / m, j = i - t * m;
+  const int64_t u = users[t];
+  const int64_t beg = rowptr[u], deg = rowptr[u + 1] - beg;
+  const int32_t n = shared[j];
+  mask[i] = (n == pos[t] || row_has(col, sorted, rowptr[0], beg, deg, n_users + n)) ? 1 : 0;
+}
+
+// n_sets * m as a count below 2^31, or false
+static bool shared_total(int64_t n_sets, int64_t m, int64_t *total) {
+  if (n_sets < 1 || m < 1 || n_sets >= INT32_MAX || m >= INT32_MAX) return false;
+  if (n_sets * m >= INT32_MAX) return false;
+  *total = n_sets * m;
+  return true;
+}
+
+}  // namespace mirec
+
+extern "C" int mirec_shared_sample(int64_t m_items, int64_t n_sets, int64_t m, uint64_t seed,
+                                   uint64_t offset, int32_t *out, mirec_stream_t stream) {
+  using namespace mirec;
+  int64_t total = 0;
+  MIREC_CHECK_ARG(out != nullptr && m_items > 0 && m_items < INT32_MAX &&
+                  shared_total(n_sets, m, &total));
+  hipLaunchKernelGGL(shared_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), m_items, total, seed, offset, out);
+  MIREC_LAUNCH_CHECK();
+  return MIREC_OK;
+}
+
+// mirec_shared_sample on the host: the same streams on CPU threads
+// (contiguous blocks of elements), the device sampler's output bit for bit.
+extern "C" int mirec_cpu_shared_sample(int64_t m_items, int64_t n_sets, int64_t m, uint64_t seed,
+                                       uint64_t offset, int32_t *out, int32_t n_threads) {
+  using namespace mirec;
+  int64_t total = 0;
+  MIREC_CHECK_ARG(out != nullptr && m_items > 0 && m_items < INT32_MAX &&
+                  shared_total(n_sets, m, &total));
+  const int nt = (int)std::max<int64_t>(
+      1, std::min<int64_t>(std::min<int64_t>(n_threads > 0 ? n_threads : 1, 64),
+                           (total + 4095) / 4096));
+  auto work = [&](int w) {
+    const int64_t a = total * w / nt, b = total * (w + 1) / nt;
+    for (int64_t i = a; i < b; ++i) out[i] = shared_sample_one(m_items, seed, offset, (uint64_t)i);
+  };
+  std::vector<std::thread> th;
+  for (int w = 1; w < nt; ++w) th.emplace_back(work, w);
+  work(0);
+  for (auto &x : th) x.join();
+  return MIREC_OK;
+}
+
+extern "C" int mirec_ssm_shared_mask(const mirec_csr_t *csr, const int32_t *users, int64_t batch,
+                                     const int32_t *pos, const int32_t *shared, int64_t m,
+                                     int64_t n_users, uint8_t *mask, mirec_stream_t stream) {
+  using namespace mirec;
+  MIREC_CHECK_ARG(csr && csr->rowptr && csr->col && users && pos && shared && mask);
+  int64_t total = 0;
+  MIREC_CHECK_ARG(shared_total(batch, m, &total) && 2 * batch + m < INT32_MAX);
+  MIREC_CHECK_ARG(n_users > 0 && n_users < INT32_MAX && csr->n_rows >= n_users);
+  hipLaunchKernelGGL(ssm_shared_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), csr->rowptr, csr->col,
+                     csr->n_sorted >= n_users ? csr->col_sorted : nullptr, users, batch, pos,
+                     shared, m, (int32_t)n_users, mask);
+  MIREC_LAUNCH_CHECK();
+  return MIREC_OK;
+}

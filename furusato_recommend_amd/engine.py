@@ -267,9 +267,11 @@ class PropagationEngine:
     fp32 summation order; ``prune=False`` runs every layer on every row."""
 
     def __init__(self, graph: Graph, dim: int, n_layers: int, max_batch: int,
-                 prune: bool = True, n_neg: int = 1):
+                 prune: bool = True, n_neg: int = 1, n_shared: int = 0):
         if int(n_neg) < 1:
             raise ValueError(f"n_neg must be at least 1, got {n_neg!r}")
+        if int(n_shared) < 0:
+            raise ValueError(f"n_shared must not be negative, got {n_shared!r}")
         if dim not in _lib.SUPPORTED_DIMS:
             raise ValueError(f"recdim={dim} not supported by the HIP engine "
                              f"(supported: {_lib.SUPPORTED_DIMS})")
@@ -283,6 +285,9 @@ class PropagationEngine:
         # negatives per positive of the sampled-softmax loss (ssm); a batch
         # has up to (2 + n_neg) * max_batch seed keys (BPR: n_neg = 1, 3B)
         self.n_neg = int(n_neg)
+        # size of the shared negative set of ssm_shared() (0: not used): such a
+        # batch has 2 * max_batch + n_shared seed keys
+        self.n_shared = int(n_shared)
         # the owner's loss, "bpr" or "ssm" (the data-parallel wrappers refuse
         # "ssm" and n_neg > 1: their seed exchange is not verified for it)
         self.loss_name = "bpr"
@@ -300,7 +305,8 @@ class PropagationEngine:
         self._bm = torch.zeros(2, words, **i32)
         self.bm_self, self.bm_hop = self._bm[0], self._bm[1]
         # S, deduplicated
-        self.self_list = torch.zeros((2 + self.n_neg) * self.max_batch, **i32)
+        B3 = max((2 + self.n_neg) * self.max_batch, 2 * self.max_batch + self.n_shared)
+        self.self_list = torch.zeros(B3, **i32)
         self.self_count = torch.zeros(1, **i32)
         self._self_cap = 0
         # S and F1 as row lists split by degree (narrow: <= narrow_max,
@@ -341,11 +347,11 @@ class PropagationEngine:
         self._masks_ready = False
         # rows of degree <= narrow_max are gathered one per lane group
         self.narrow_max = 64
-        B3 = (2 + self.n_neg) * self.max_batch
         self.seed_p = torch.empty(B3, D, **f32)
         self.seed_e = torch.empty(B3, D, **f32)
         self.coef = torch.empty(self.n_neg * self.max_batch, **f32)
         self.coef_pos = self.g_u = None  # ssm()'s own buffers, made on first use
+        self._shared = None              # ssm_shared()'s, likewise
         self.softplus = torch.empty(self.max_batch, **f32)
         self.reg = torch.empty(self.max_batch, **f32)
         self.keys = torch.empty(B3, **i32)
@@ -425,6 +431,22 @@ class PropagationEngine:
         if nb.value > self._ws_bytes:
             self._ws = torch.empty(nb.value, dtype=torch.uint8, device=self.g.device)
             self._ws_bytes = nb.value
+
+    def _ensure_ssm_shared(self, batch: int, m: int):
+        if self._shared is None:
+            dev, B, M = self.g.device, self.max_batch, self.n_shared
+            f32 = dict(dtype=torch.float32, device=dev)
+            self._shared = dict(coef=torch.empty(B * M, **f32), coef_pos=torch.empty(B, **f32),
+                                g=torch.empty(B + M, self.dim, **f32),
+                                reg=torch.empty(M, **f32),
+                                mask=torch.empty(B * M, dtype=torch.uint8, device=dev))
+        nb = ctypes.c_size_t(0)
+        check(lib.mirec_ssm_shared_seed_workspace(batch, m, self.g.n_nodes, ctypes.byref(nb)),
+              "ssm_shared_seed_workspace")
+        if nb.value > self._ws_bytes:
+            self._ws = torch.empty(nb.value, dtype=torch.uint8, device=self.g.device)
+            self._ws_bytes = nb.value
+        return self._shared
 
     def _prop(self, *, in_mode, x_in=None, seed_in=None, seed=None, addend=None, seed2=None,
               divisor=1.0, out=None, xs_out=None, adam=None, param=None, graph=None,
@@ -920,6 +942,77 @@ class PropagationEngine:
         self._seeds = (self.seed_p, self.seed_e, self.keys_sorted, (2 + K) * B)
         return self.loss
 
+    # ------------------------------- sampled softmax, shared negative set
+    def _ssm_shared_shape(self, users, shared):
+        """(B, M) of a shared-negative batch: int32 ``shared`` of shape [M],
+        1 <= M <= n_shared."""
+        B = int(users.shape[0])
+        if B > self.max_batch:
+            raise ValueError(f"batch {B} > engine max_batch {self.max_batch}")
+        if shared.dim() != 1 or int(shared.shape[0]) < 1:
+            raise ValueError(f"ssm_shared: shared must have shape [M], M >= 1, got "
+                             f"{tuple(shared.shape)}")
+        M = int(shared.shape[0])
+        if M > self.n_shared:
+            raise ValueError(f"ssm_shared: {M} shared negatives > engine n_shared "
+                             f"{self.n_shared}")
+        if shared.dtype != torch.int32 or not shared.is_contiguous():
+            raise ValueError("ssm_shared: shared must be a contiguous int32 tensor")
+        return B, M
+
+    def frontier_ssm_shared(self, users, pos, shared):
+        """compute_frontier of a shared-negative batch: its 2B + M node ids are
+        written on the device (mirec_ssm_shared_keys) and given to the
+        key-list frontier."""
+        B, M = self._ssm_shared_shape(users, shared)
+        check(lib.mirec_ssm_shared_keys(users.data_ptr(), pos.data_ptr(), shared.data_ptr(), B, M,
+                                        self.g.n_users, self.keys.data_ptr(),
+                                        _lib.stream_handle()), "ssm_shared_keys")
+        self.compute_frontier(keys=self.keys, n_keys=2 * B + M)
+
+    def ssm_shared(self, out: torch.Tensor, emb: torch.Tensor, users, pos, shared, decay: float,
+                   temp: float, loss_accum: torch.Tensor | None = None,
+                   grad_scale: float = 1.0) -> torch.Tensor:
+        """Sampled-softmax loss + gradient seeds for one batch whose B pairs
+        share one list of negatives: int32 device ``users`` / ``pos`` [B] and
+        ``shared`` [M] (M <= n_shared).  A candidate that is a training
+        positive of the pair's user, or the pair's ``pos`` itself, is left
+        out of that pair's softmax; the shared rows' norms enter the reg term
+        once per slot."""
+        B, M = self._ssm_shared_shape(users, shared)
+        if not (float(temp) > 0.0 and math.isfinite(float(temp))):
+            raise ValueError(f"ssm_shared: temp must be positive and finite, got {temp!r}")
+        if not self._masks_ready:
+            self.frontier_ssm_shared(users, pos, shared)  # the seed set S for the backward
+        b = self._ensure_ssm_shared(B, M)
+        st = _lib.stream_handle()
+        g = self.g
+        check(lib.mirec_ssm_shared_mask(g.csr_ptr(), users.data_ptr(), B, pos.data_ptr(),
+                                        shared.data_ptr(), M, g.n_users, b["mask"].data_ptr(),
+                                        st), "ssm_shared_mask")
+        check(lib.mirec_ssm_shared_forward(out.data_ptr(), emb.data_ptr(), g.n_nodes, g.n_users,
+                                           self.dim, B, M, users.data_ptr(), pos.data_ptr(),
+                                           shared.data_ptr(), b["mask"].data_ptr(), float(temp),
+                                           float(grad_scale), b["coef"].data_ptr(),
+                                           b["coef_pos"].data_ptr(), self.softplus.data_ptr(),
+                                           self.reg.data_ptr(), b["reg"].data_ptr(),
+                                           b["g"].data_ptr(), self.keys.data_ptr(),
+                                           self.vals.data_ptr(), st), "ssm_shared_forward")
+        check(lib.mirec_ssm_shared_loss(self.softplus.data_ptr(), self.reg.data_ptr(),
+                                        b["reg"].data_ptr(), B, M, float(decay),
+                                        self.loss.data_ptr(), ptr(loss_accum), st),
+              "ssm_shared_loss")
+        check(lib.mirec_ssm_shared_seed(out.data_ptr(), emb.data_ptr(), g.n_nodes, g.n_users,
+                                        self.dim, B, M, users.data_ptr(),
+                                        b["coef_pos"].data_ptr(), b["g"].data_ptr(),
+                                        self.keys.data_ptr(), self.vals.data_ptr(), float(decay),
+                                        float(grad_scale), self.L, self.slot.data_ptr(),
+                                        self.seed_p.data_ptr(), self.seed_e.data_ptr(),
+                                        self.keys_sorted.data_ptr(), self._ws.data_ptr(),
+                                        self._ws_bytes, st), "ssm_shared_seed")
+        self._seeds = (self.seed_p, self.seed_e, self.keys_sorted, 2 * B + M)
+        return self.loss
+
     # ----------------------------------------------- data-parallel exchange
     def export_seeds(self):
         """Local seeds as fixed-size rows for an all-gather: (keys [3B] int32,
@@ -1081,6 +1174,38 @@ class PropagationEngine:
             if dropout is not None:
                 self.set_dropout(None)
         return loss
+
+    def train_step_ssm_shared(self, emb: torch.Tensor, adam: AdamState, users, pos, shared,
+                              decay: float, temp: float,
+                              loss_accum: torch.Tensor | None = None,
+                              dropout=None) -> torch.Tensor:
+        """train_step_ssm with one shared negative set ``shared`` [M] for the
+        whole batch: frontier of its 2B + M nodes, (pruned) forward,
+        ssm_shared(), backward, fused Adam; no host synchronisation."""
+        if dropout is not None:
+            self.set_dropout(*dropout)
+        try:
+            self.frontier_ssm_shared(users, pos, shared)
+            out = self.forward(emb, pruned=self.prune)
+            loss = self.ssm_shared(out, emb, users, pos, shared, decay, temp, loss_accum)
+            self.backward(emb, adam=adam)
+        finally:
+            if dropout is not None:
+                self.set_dropout(None)
+        return loss
+
+
+def sample_shared(m_items: int, n_sets: int, m: int, seed: int, offset: int, out):
+    """``n_sets`` shared negative sets of ``m`` item ids into int32 ``out``
+    [n_sets, m] (mirec_shared_sample, or its host twin for a host tensor):
+    uniform over [0, m_items), no rejection."""
+    s, o = ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_uint64(offset & (2**64 - 1))
+    if out.device.type == "cuda":
+        check(lib.mirec_shared_sample(int(m_items), int(n_sets), int(m), s, o, out.data_ptr(),
+                                      _lib.stream_handle()), "shared_sample")
+    else:
+        check(lib.mirec_cpu_shared_sample(int(m_items), int(n_sets), int(m), s, o,
+                                          out.data_ptr(), 1), "cpu_shared_sample")
 
 
 def edge_dot(graph: Graph, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor):

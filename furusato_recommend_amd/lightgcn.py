@@ -20,6 +20,10 @@ BPR: ``config["neg_size"]`` negatives per positive and the temperature
 §18); ``stageOne`` / ``OneEpoch`` / ``sample`` then carry ``neg`` of shape
 [n, neg_size], and ``softmax_loss`` is the differentiable form.
 ``LightGCNSSM`` (lgcnssm.py, 'lgnssm') is this class with that default.
+``config["neg_shared"] = M`` (with the "ssm" loss) draws one set of M
+negatives per batch instead, shared by all its pairs (train_step_ssm_shared,
+DESIGN.md §19): ``stageOne`` takes ``neg`` [M], ``OneEpoch`` and ``sample``
+one set per batch, [ceil(n / bpr_batch_size), M].
 
 ``rAdjGCN`` (radj.py) is this class on a graph with the r-adjusted
 normalisation; ``LightGCN`` itself ignores ``config["r"]``, as the
@@ -30,7 +34,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .engine import AdamState, PropagationEngine, sample_pairs, sample_triples
+from .engine import (AdamState, PropagationEngine, check, sample_pairs, sample_shared,
+                     sample_triples)
 from .graph import DEFAULT_SPLIT, Graph, positive_probs
 
 
@@ -148,6 +153,21 @@ class LightGCN(nn.Module):
                              f"got {self.ssm_temp!r}")
         if self.loss_name == "bpr":
             self.neg_size = 1  # the BPR loss takes one negative: the key is not read
+        # config["neg_shared"] = M: one set of M negatives per batch, shared
+        # by all its pairs, in place of neg_size negatives per pair (DESIGN.md
+        # §19); absent or None: per-pair negatives as above
+        neg_shared = _config_get(config, "neg_shared", default=None)
+        if neg_shared is not None:
+            if int(neg_shared) != neg_shared or int(neg_shared) < 1:
+                raise ValueError(f"config['neg_shared'] must be an integer >= 1, "
+                                 f"got {neg_shared!r}")
+            if self.loss_name != "ssm":
+                raise ValueError("config['neg_shared'] needs config['loss'] = 'ssm', "
+                                 f"got {self.loss_name!r}")
+            if self.neg_size > 1:
+                raise ValueError("config['neg_shared'] with config['neg_size'] > 1: "
+                                 "two ways to ask for negatives")
+        self.neg_shared = None if neg_shared is None else int(neg_shared)
         self.graph = Graph.from_interactions(dataset.trainUser, dataset.trainItem,
                                              self.num_users, self.num_items, self.device,
                                              split=int(config.get("csr_split", DEFAULT_SPLIT)),
@@ -158,7 +178,7 @@ class LightGCN(nn.Module):
         self.engine = PropagationEngine(self.graph, self.latent_dim, self.num_layers,
                                         int(config.get("bpr_batch_size", 2048)),
                                         prune=bool(config.get("prune", True)),
-                                        n_neg=self.neg_size)
+                                        n_neg=self.neg_size, n_shared=self.neg_shared or 0)
         self.engine.loss_name = self.loss_name
         self.engine.edge_dropout = self.keep_prob if self.dropout else None
         self._loss_accum = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -221,7 +241,14 @@ class LightGCN(nn.Module):
         |E_neg|^2) / n over the gathered ego rows (a negative drawn twice
         counts twice), as ``bpr_loss`` returns its pair.  What
         model/lgcnssm.py:98-118 evidently means: its body is still the BPR
-        softplus, which this equals for K = 1, ssm_temp = 1."""
+        softplus, which this equals for K = 1, ssm_temp = 1.
+
+        Under config["neg_shared"] ``neg`` is the shared list [M]: the
+        softmax of pair t runs over s+_t and the candidates that are neither
+        a training positive of its user nor its ``pos`` (the mask of
+        mirec_ssm_shared_mask), and reg_loss counts each shared slot once."""
+        if self.neg_shared is not None:
+            return self._softmax_loss_shared(users, pos, neg)
         users, pos, neg = users.long(), pos.long(), self._neg2d(neg, len(users)).long()
         all_users, all_items = self.forward()
         ue, pe, ne = all_users[users], all_items[pos], all_items[neg]
@@ -234,6 +261,39 @@ class LightGCN(nn.Module):
         sn = torch.einsum("bd,bkd->bk", ue, ne) / self.ssm_temp
         lse = torch.logsumexp(torch.cat([sp[:, None], sn], dim=1), dim=1)
         return torch.mean(lse - sp), reg_loss
+
+    def _softmax_loss_shared(self, users, pos, shared):
+        shared = self._shared1d(shared)
+        u32, p32, s32 = self._as_i32(users), self._as_i32(pos), self._as_i32(shared)
+        B, M = len(u32), len(s32)
+        mask = torch.empty(B, M, dtype=torch.uint8, device=self.device)
+        from . import _lib
+        check(_lib.lib.mirec_ssm_shared_mask(self.graph.csr_ptr(), u32.data_ptr(), B,
+                                             p32.data_ptr(), s32.data_ptr(), M, self.num_users,
+                                             mask.data_ptr(), _lib.stream_handle()),
+              "ssm_shared_mask")
+        users, pos, shared = u32.long(), p32.long(), s32.long()
+        all_users, all_items = self.forward()
+        ue, pe, ne = all_users[users], all_items[pos], all_items[shared]
+        u0 = self.all_embedding(users)
+        p0 = self.all_embedding(pos + self.num_users)
+        n0 = self.all_embedding(shared + self.num_users)
+        reg_loss = (0.5 * (u0.norm(2).pow(2) + p0.norm(2).pow(2) + n0.norm(2).pow(2))
+                    / float(B))
+        sp = torch.sum(ue * pe, dim=1) / self.ssm_temp
+        sn = (ue @ ne.t()) / self.ssm_temp
+        sn = sn.masked_fill(mask.bool(), float("-inf"))
+        lse = torch.logsumexp(torch.cat([sp[:, None], sn], dim=1), dim=1)
+        return torch.mean(lse - sp), reg_loss
+
+    def _shared1d(self, neg):
+        """``neg`` as the shared list [neg_shared] of one batch."""
+        if not torch.is_tensor(neg):
+            neg = torch.as_tensor(neg)
+        if neg.dim() != 1 or int(neg.shape[0]) != self.neg_shared:
+            raise ValueError(f"neg must have shape [{self.neg_shared}] with "
+                             f"config['neg_shared'], got {tuple(neg.shape)}")
+        return neg
 
     def _neg2d(self, neg, n: int):
         """``neg`` as the [n, K] tensor of the sampled-softmax paths
@@ -288,8 +348,14 @@ class LightGCN(nn.Module):
     @torch.no_grad()
     def stageOne(self, user, pos, neg, loss_accum=None):
         """One fused BPR step (model/lgcn.py:127-133); returns the loss tensor.
-        With config["loss"] = "ssm": one sampled-softmax step, ``neg`` [n, K]."""
+        With config["loss"] = "ssm": one sampled-softmax step, ``neg`` [n, K];
+        with config["neg_shared"]: ``neg`` is the batch's shared list [M]."""
         w = self.all_embedding.weight
+        if self.neg_shared is not None:
+            return self.engine.train_step_ssm_shared(
+                w, self.optim, self._as_i32(user), self._as_i32(pos),
+                self._as_i32(self._shared1d(neg)), float(self.config["decay"]), self.ssm_temp,
+                loss_accum, dropout=self._next_dropout()).clone()
         if self.loss_name == "ssm":
             neg = self._as_i32(self._neg2d(neg, len(user)))
             return self.engine.train_step_ssm(w, self.optim, self._as_i32(user),
@@ -312,6 +378,23 @@ class LightGCN(nn.Module):
         B = int(self.config["bpr_batch_size"])
         n = len(user)
         total_batch = n // B + 1
+        if self.neg_shared is not None:
+            # one shared set per batch: neg [ceil(n / B), M]
+            if not torch.is_tensor(neg):
+                neg = torch.as_tensor(neg)
+            n_sets = (n + B - 1) // B
+            if neg.dim() != 2 or tuple(neg.shape) != (n_sets, self.neg_shared):
+                raise ValueError(f"neg must have shape [{n_sets}, {self.neg_shared}] with "
+                                 f"config['neg_shared'], got {tuple(neg.shape)}")
+            user, pos, neg = self._as_i32(user), self._as_i32(pos), self._as_i32(neg)
+            self._loss_accum.zero_()
+            for b, i in enumerate(range(0, n, B)):
+                self.engine.train_step_ssm_shared(self.all_embedding.weight, self.optim,
+                                                  user[i:i + B], pos[i:i + B], neg[b],
+                                                  float(self.config["decay"]), self.ssm_temp,
+                                                  self._loss_accum,
+                                                  dropout=self._next_dropout())
+            return self._loss_accum[0] / total_batch
         if self.loss_name == "ssm":
             user, pos = self._as_i32(user), self._as_i32(pos)
             neg = self._as_i32(self._neg2d(neg, n))
@@ -335,10 +418,25 @@ class LightGCN(nn.Module):
                n_shards: int = 1):
         """On-device UniformSample: int32 (users, pos, neg) device tensors;
         with config["loss"] = "ssm" ``neg`` is [n_triples, neg_size]
-        (mirec_ssm_sample: the same users, positives and first negatives)."""
+        (mirec_ssm_sample: the same users, positives and first negatives);
+        with config["neg_shared"] = M it is [ceil(n_triples / bpr_batch_size),
+        M], one shared set per batch (mirec_shared_sample of the same seed and
+        offset), beside mirec_bpr_sample_ex's users and positives."""
         dev = self.device
         u = torch.empty(n_triples, dtype=torch.int32, device=dev)
         p = torch.empty_like(u)
+        if self.neg_shared is not None:
+            # the BPR sampler's users and positives (its negative is dropped)
+            # and one shared set per batch of bpr_batch_size pairs
+            n = torch.empty_like(u)
+            err = torch.zeros(1, dtype=torch.int32, device=dev)
+            sample_triples(self.graph, n_triples, seed, offset, u, p, n, err, shard, n_shards)
+            self._sample_err = err
+            B = int(self.config.get("bpr_batch_size", 2048))
+            n_sets = max(1, (n_triples + B - 1) // B)
+            sets = torch.empty(n_sets, self.neg_shared, dtype=torch.int32, device=dev)
+            sample_shared(self.num_items, n_sets, self.neg_shared, seed, offset, sets)
+            return u, p, sets
         if self.loss_name == "ssm":
             n = torch.empty(n_triples, self.neg_size, dtype=torch.int32, device=dev)
             err = torch.zeros(1, dtype=torch.int32, device=dev)

@@ -753,6 +753,91 @@ int mirec_ssm_seed(const float *out, const float *emb, int64_t n_nodes, int64_t 
                    size_t workspace_bytes, mirec_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* Sampled softmax with one set of m negatives per batch, shared by all B   */
+/* pairs (csrc/ssm_shared.hip)                               */
+/* ------------------------------------------------------------------------ */
+
+/* Pairs (users[t], pos[t]), t < B, and the shared item ids shared[j], j < m
+ * (no n_users offset; drawn with replacement, a repeated id counts twice
+ * everywhere).  Occurrence t is the user of pair t, B + t its positive,
+ * 2B + j shared slot j: keys[2B + m] = users, n_users + pos, n_users +
+ * shared — the batch's node list for mirec_frontier's key form.
+ * Every entry point of this section returns MIREC_ERR_ARG for a NULL
+ * pointer, batch < 1, m < 1, B m >= 2^31 or 2B + m >= 2^31 (the forward also
+ * for temp <= 0 or not finite and an unsupported dim) and then writes
+ * nothing. */
+int mirec_ssm_shared_keys(const int32_t *users, const int32_t *pos, const int32_t *shared,
+                          int64_t batch, int64_t m, int64_t n_users, int32_t *keys,
+                          mirec_stream_t stream);
+
+/* mask[t * m + j] = 1 iff shared[j] is a training positive of users[t] (an
+ * entry of CSR row users[t]: binary search in csr->col_sorted when the CSR
+ * carries it for the user rows, else a scan of the row, as the samplers
+ * test a negative) or shared[j] == pos[t]; else 0.  A masked candidate is
+ * left out of pair t's softmax. */
+int mirec_ssm_shared_mask(const mirec_csr_t *csr, const int32_t *users, int64_t batch,
+                          const int32_t *pos, const int32_t *shared, int64_t m,
+                          int64_t n_users, uint8_t *mask, mirec_stream_t stream);
+
+/* With s+ = <out_u, out_p> / temp, s_j = <out_u, out_nj> / temp and the
+ * softmax of pair t taken over s+ and its unmasked s_j (max-subtracted):
+ *   terms[t]      = logsumexp - s+      (exactly 0 when every j is masked)
+ *   coef[t*m + j] = grad_scale * weight of candidate j / (B temp), exactly 0
+ *                   when masked;  coef_pos[t] = sum_j coef[t*m + j]
+ *   reg[t]        = 1/2 (|e_u|^2 + |e_p|^2);  reg_shared[j] = 1/2 |e_nj|^2
+ *   g[t, :]       = sum_j coef[t*m + j] out_nj - coef_pos[t] out_p   (t < B)
+ *   g[B + j, :]   = sum_t coef[t*m + j] out_u_t                      (j < m)
+ * and the 2B + m seed (keys, vals) = (node id, occurrence index).  Every
+ * sum has one fixed order (scores: d ascending; the row sums over j: lane l
+ * of 64 takes j = l, l + 64, .., then a xor tree; g: j, resp. t, ascending,
+ * then the positive), none depends on the launch shape or on the other
+ * pairs of the batch; no float atomics.  The loss is mirec_ssm_shared_loss. */
+int mirec_ssm_shared_forward(const float *out, const float *emb, int64_t n_nodes,
+                             int64_t n_users, int32_t dim, int64_t batch, int64_t m,
+                             const int32_t *users, const int32_t *pos, const int32_t *shared,
+                             const uint8_t *mask, float temp, float grad_scale, float *coef,
+                             float *coef_pos, float *terms, float *reg, float *reg_shared,
+                             float *g, int32_t *keys, int32_t *vals, mirec_stream_t stream);
+
+/* loss_out[0] = sum_t terms[t] / B + decay * (sum_t reg[t] + sum_j
+ * reg_shared[j]) / B (one workgroup, fixed partition and tree); if
+ * loss_accum != NULL also loss_accum[0] += that.  A shared row's norm counts
+ * once per slot, not once per pair: with m = 1 this is not mirec_bpr_loss's
+ * reg, which counts the negative's norm B times. */
+int mirec_ssm_shared_loss(const float *terms, const float *reg, const float *reg_shared,
+                          int64_t batch, int64_t m, float decay, float *loss_out,
+                          float *loss_accum, mirec_stream_t stream);
+
+/* Scratch bytes mirec_ssm_shared_seed needs. */
+int mirec_ssm_shared_seed_workspace(int64_t batch, int64_t m, int64_t n_nodes, size_t *bytes);
+
+/* Gradient seeds from mirec_ssm_shared_forward's outputs, laid out as
+ * mirec_ssm_seed's: stable sort of the 2B + m pairs (the small sort up to
+ * 8 192 pairs, the radix sort above), slot[node] = q at the head of every
+ * run (slot all -1 on entry), and
+ *   seed_p[q] = (sum over the node's occurrences, in occurrence order, of
+ *                1 * g[t] | -coef_pos[t] * out_u | 1 * g[B + j]
+ *                for a user | positive | shared occurrence) / (L+1)
+ *   seed_e[q] = decay * (#occurrences) * emb[node] / B * grad_scale
+ * keys_sorted[2B + m] feeds mirec_bpr_seed_reset.  MIREC_ERR_WORKSPACE on a
+ * short workspace. */
+int mirec_ssm_shared_seed(const float *out, const float *emb, int64_t n_nodes, int64_t n_users,
+                          int32_t dim, int64_t batch, int64_t m, const int32_t *users,
+                          const float *coef_pos, const float *g, const int32_t *keys,
+                          const int32_t *vals, float decay, float grad_scale, int32_t n_layers,
+                          int32_t *slot, float *seed_p, float *seed_e, int32_t *keys_sorted,
+                          void *workspace, size_t workspace_bytes, mirec_stream_t stream);
+
+/* n_sets shared sets of m item ids: out[b * m + j] uniform over [0,
+ * m_items), with replacement and without rejection.  Element b * m + j is
+ * one draw of the stream keyed by (seed, the sampler's own domain tag,
+ * offset) at counter b * m + j: set b does not depend on n_sets or the
+ * launch shape, and calls with different offsets are independent.
+ * MIREC_ERR_ARG: out NULL, m_items < 1, n_sets < 1, m < 1, n_sets m >= 2^31. */
+int mirec_shared_sample(int64_t m_items, int64_t n_sets, int64_t m, uint64_t seed,
+                        uint64_t offset, int32_t *out, mirec_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* Adam (torch.optim.Adam, amsgrad=False, weight_decay=0)                   */
 /* ------------------------------------------------------------------------ */
 
@@ -1397,6 +1482,11 @@ int mirec_cpu_ssm_sample(const int64_t *rowptr, const int32_t *col, const int32_
                          int32_t n_neg, uint64_t seed, uint64_t offset, int32_t shard,
                          int32_t n_shards, int32_t *users, int32_t *pos, int32_t *neg,
                          int32_t *err, int32_t n_threads);
+
+/* mirec_shared_sample on the host: the same streams, the same output bit for
+ * bit, whatever n_threads. */
+int mirec_cpu_shared_sample(int64_t m_items, int64_t n_sets, int64_t m, uint64_t seed,
+                            uint64_t offset, int32_t *out, int32_t n_threads);
 
 /* mirec_bpr_sample_capped_ex on the host (the ddp_lgcn.py epoch sampler for
  * a CPU model): the same candidate streams, so users / pos / neg (capacity

@@ -4,17 +4,20 @@ The bench.py C2 workload (1 M users, 100 k items, 20 M interactions, uniform;
 d = 64, L = 3, B = 2048, pruning on, one sampler call + one fused step per
 step) run in one process on one device: BPR legs (mirec_bpr_sample_ex +
 train_step) alternating with sampled-softmax legs (mirec_ssm_sample +
-train_step_ssm) at every --neg K: (bpr, K1, K2, ..., bpr, K1, ...), each
---steps timed steps after --warmup; the spread between the BPR legs is the
+train_step_ssm) at every --neg K and shared-negative legs (mirec_bpr_sample_ex
++ mirec_shared_sample + train_step_ssm_shared) at every
+--shared M: (bpr, K1, K2, ..., M1, M2, ..., bpr, ...), each --steps timed steps after --warmup; the spread between the BPR legs is the
 yardstick for the others.  Every case has a model of its own on the one
 shared dataset (the engines' buffers are sized by n_neg).  One JSON line per
 leg, then per case a summary line, the device time of its loss + seed stage
-(mirec_ssm_forward / mirec_bpr_loss / mirec_ssm_seed between two events,
-median over --stage-steps steps run after the legs) and the mean sizes of
+(mirec_ssm_forward / mirec_bpr_loss / mirec_ssm_seed, resp. the mask, forward,
+loss and seed calls of ssm_shared(), between two events, median over --stage-steps steps run after the legs) and the mean sizes of
 the batch's node set S and of its one-hop frontier S ∪ N(S); appended to
 --out.
 
     python tools/bench_ssm.py --out profiles/ssm_bench_lines.txt
+    python tools/bench_ssm.py --neg 8 64 --shared 512 2048 4096 \
+        --out profiles/ssm_shared_bench_lines.txt
 """
 from __future__ import annotations
 
@@ -29,7 +32,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from furusato_recommend_amd import LightGCN, SyntheticBipartite  # noqa: E402
-from furusato_recommend_amd.engine import sample_pairs, sample_triples  # noqa: E402
+from furusato_recommend_amd.engine import (sample_pairs, sample_shared,  # noqa: E402
+                                           sample_triples)
 
 
 def main():
@@ -41,6 +45,8 @@ def main():
     ap.add_argument("--layers", type=int, default=3)
     ap.add_argument("--batch", type=int, default=2048)
     ap.add_argument("--neg", type=int, nargs="+", default=[1, 8, 64])
+    ap.add_argument("--shared", type=int, nargs="*", default=[],
+                    help="sizes M of a negative set shared by the batch (neg_shared)")
     ap.add_argument("--temp", type=float, default=0.2)
     ap.add_argument("--legs", type=int, default=3, help="legs per case")
     ap.add_argument("--steps", type=int, default=100)
@@ -60,10 +66,14 @@ def main():
     cases = {"bpr": LightGCN(cfg, ds)}
     for k in args.neg:
         cases[f"ssm{k}"] = LightGCN(dict(cfg, loss="ssm", neg_size=k, ssm_temp=args.temp), ds)
+    for k in args.shared:
+        cases[f"shared{k}"] = LightGCN(dict(cfg, loss="ssm", neg_shared=k, ssm_temp=args.temp), ds)
     u = torch.empty(B, dtype=torch.int32, device=dev)
     p = torch.empty_like(u)
-    negs = {c: torch.empty((B, m.neg_size) if m.loss_name == "ssm" else (B,), dtype=torch.int32,
-                           device=dev) for c, m in cases.items()}
+    unused = torch.empty_like(u)  # the BPR sampler's negative under neg_shared
+    negs = {c: torch.empty((m.neg_shared,) if m.neg_shared else (B, m.neg_size)
+                           if m.loss_name == "ssm" else (B,), dtype=torch.int32, device=dev)
+            for c, m in cases.items()}
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     done = {c: 0 for c in cases}
 
@@ -72,24 +82,33 @@ def main():
         of events recorded around the loss + seed stage."""
         m, n = cases[c], negs[c]
         eng, emb = m.engine, m.all_embedding.weight.data
-        if m.loss_name == "ssm":
+        if m.neg_shared:
+            sample_triples(m.graph, B, args.seed, done[c] * B, u, p, unused, err)
+            sample_shared(m.num_items, 1, m.neg_shared, args.seed, done[c], n)
+        elif m.loss_name == "ssm":
             sample_pairs(m.graph, B, m.neg_size, args.seed, done[c] * B, u, p, n, err)
         else:
             sample_triples(m.graph, B, args.seed, done[c] * B, u, p, n, err)
         done[c] += 1
         if split is None:
-            if m.loss_name == "ssm":
+            if m.neg_shared:
+                eng.train_step_ssm_shared(emb, m.optim, u, p, n, cfg["decay"], m.ssm_temp)
+            elif m.loss_name == "ssm":
                 eng.train_step_ssm(emb, m.optim, u, p, n, cfg["decay"], m.ssm_temp)
             else:
                 eng.train_step(emb, m.optim, u, p, n, cfg["decay"])
             return
-        if m.loss_name == "ssm":
+        if m.neg_shared:
+            eng.frontier_ssm_shared(u, p, n)
+        elif m.loss_name == "ssm":
             eng.frontier_ssm(u, p, n)
         else:
             eng.compute_frontier(u, p, n)
         out = eng.forward(emb, pruned=eng.prune)
         split[0].record()
-        if m.loss_name == "ssm":
+        if m.neg_shared:
+            eng.ssm_shared(out, emb, u, p, n, cfg["decay"], m.ssm_temp)
+        elif m.loss_name == "ssm":
             eng.ssm(out, emb, u, p, n, cfg["decay"], m.ssm_temp)
         else:
             eng.bpr(out, emb, u, p, n, cfg["decay"])
@@ -117,7 +136,7 @@ def main():
     for c, m in cases.items():
         legs = [x["ms_per_step"] for x in lines if x["case"] == c]
         s = {"workload": f"C2-uniform-d{args.dim}-L{args.layers}-B{B}", "case": c,
-             "neg_size": m.neg_size, "temp": m.ssm_temp if m.loss_name == "ssm" else None,
+             "neg_size": m.neg_size, "neg_shared": m.neg_shared, "temp": m.ssm_temp if m.loss_name == "ssm" else None,
              "ms": legs, "mean_ms": round(sum(legs) / len(legs), 4),
              "bpr_spread_ms": round(max(base) - min(base), 4),
              "ratio_to_bpr": round(sum(legs) / len(legs) / (sum(base) / len(base)), 4)}
