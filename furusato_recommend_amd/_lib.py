@@ -390,6 +390,10 @@ SIGNATURES = {
     "mirec_score_topk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p,
                                  c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),
+    "mirec_score_rank_workspace": (c_int64, [c_int64, c_int64, c_int64, c_int32]),
+    "mirec_score_rank": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mirec_topk_masked": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                   c_int32, c_void_p, c_void_p, c_void_p]),
     "mirec_bpr_sample_capped_workspace": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),

@@ -11,7 +11,9 @@ the proprietary product-name / CSV side outputs.
                  (utils.shuffle); on-device draws are i.i.d., so the shuffle
                  is a distributional no-op and is skipped.
   test()         Recall / Precision / NDCG / HR @ topks (trainer.py:115-170)
-                 through evaluate.evaluate (one propagation, HIP top-k).
+                 through evaluate.evaluate (one propagation, HIP top-k);
+                 config["eval_rank"]: through evaluate.evaluate_ranked
+                 (exact ranks: the same four at any k, plus "mrr" and "auc").
   train_epoch()  test once, then epochs with a test every test_span
                  (trainer.py:237-258); best recall@topks[0] checkpoints.
 """
@@ -21,7 +23,7 @@ import os
 
 import torch
 
-from .evaluate import evaluate
+from .evaluate import evaluate, evaluate_ranked
 
 
 class Trainer:
@@ -64,8 +66,9 @@ class Trainer:
 
     def test(self):
         self.model.eval()
-        res = evaluate(self.model, self.dataset.testDict, self.topks,
-                       int(self.config.get("test_u_batch_size", 10000)))
+        fn = evaluate_ranked if self.config.get("eval_rank") else evaluate
+        res = fn(self.model, self.dataset.testDict, self.topks,
+                 int(self.config.get("test_u_batch_size", 10000)))
         if res["recall"][0] > self.max_recall:
             self.max_recall = float(res["recall"][0])
             path = self.config.get("checkpoint_path")

@@ -1460,6 +1460,37 @@ int mirec_score_topk(const float *user_emb, int64_t n_eval, const float *item_em
                      int64_t n_users, int32_t k, int32_t *topk_idx, float *topk_val,
                      void *workspace, size_t workspace_bytes, mirec_stream_t stream);
 
+/* Streamed full-rank evaluation: the exact position of every
+ * held-out (user, item) pair among the user's non-train items, as integer
+ * counts, WITHOUT materialising the scores.  User slot r (row r of user_emb,
+ * user id users[r]) owns the pairs tptr[r] .. tptr[r + 1] - 1 of `targets`
+ * (item ids, distinct per user; tptr[0] = 0, non-decreasing).  With s_j =
+ * <user_emb[r], item_emb[j]> — bitwise mirec_score_topk's score of the same
+ * (row, item) — and J the items that are not train positives of users[r]
+ * (csr row users[r], entries n_users + item; csr == NULL: every item), pair
+ * t of slot r gets
+ *   score    = s_t
+ *   masked   = 1 if t is not in J (or not an item id); its counts are then
+ *              unspecified
+ *   gt       = #{j in J : s_j >  s_t}
+ *   eq       = #{j in J : s_j == s_t}          (t itself included: >= 1)
+ *   eq_lower = #{j in J, j < t : s_j == s_t}
+ * so 1 + gt + eq_lower is t's rank in mirec_score_topk's order (score
+ * descending, ties to the lower item id).  dim in {16, 32, 64, 128, 256}.
+ * tptr is a HOST array [n_eval + 1] (the pair count tptr[n_eval] sizes the
+ * launches; the call copies the array to the workspace on `stream`, so a
+ * pinned tptr must stay unchanged until the stream has passed the call);
+ * every other pointer is a device pointer, the outputs [tptr[n_eval]] each.
+ * No pairs: returns at once, reading and launching nothing.  workspace:
+ * mirec_score_rank_workspace bytes, 16-byte aligned. */
+int64_t mirec_score_rank_workspace(int64_t n_eval, int64_t n_targets, int64_t m_items,
+                                   int32_t dim);
+int mirec_score_rank(const float *user_emb, int64_t n_eval, const float *item_emb,
+                     int64_t m_items, int32_t dim, const int32_t *users, const int64_t *tptr,
+                     const int32_t *targets, const mirec_csr_t *csr, int64_t n_users,
+                     float *score, int32_t *gt, int32_t *eq, int32_t *eq_lower, uint8_t *masked,
+                     void *ws, size_t ws_bytes, mirec_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* Host (CPU) path of configuration C1 (model/MF.py BPR, "CPU single-process", */
 /* BASELINE configs[0]): host pointers, no stream, n_threads worker threads.  */
