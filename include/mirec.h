@@ -276,6 +276,30 @@ int mirec_edge_keep_mask(const int64_t *rowptr, const int32_t *col, int64_t n_ro
                          uint64_t seed, float keep_prob, int32_t transposed,
                          uint8_t *keep);
 
+/* Element dropout (dropout_p / seed of the GraphSAGE hop means, the table
+ * gradient's mean groups and the SASRec row tail): a pure function of (seed,
+ * element index), so nothing is stored and a backward given the same seed
+ * recomputes the forward's mask.  With mix64 as above (uint64 arithmetic):
+ *   key    = mix64(seed ^ 0xA24BAED4963EE407)
+ *   thresh = floor((double)dropout_p * 65536 + 0.5), raised to 1 when
+ *            dropout_p > 0 gives 0, capped at 65535; dropout_p = 0: no mask
+ *   scale  = 1.0f / (1.0f - dropout_p) in float (1 when dropout_p = 0)
+ * element idx is kept iff
+ *   ((mix64(key + (idx >> 2)) >> (16 * (idx & 3))) & 0xffff) >= thresh
+ * (key + (idx >> 2) wraps mod 2^64; the four elements of an aligned quad are
+ * the four 16-bit slices of one hash).  A kept element is multiplied by scale,
+ * a dropped one is 0.  dropout_p must lie in [0, 1) (MIREC_ERR_ARG otherwise,
+ * NaN included).  Element index:
+ *   (t*k + c) * dim + col   mirec_fanout_mean and its backward,
+ *                           mirec_fanout_mean_gather and both its backwards,
+ *                           the mean groups of mirec_table_grad_*: column col
+ *                           of child c of target t
+ *   row * d + col           mirec_resnorm_fwd / _bwd, mirec_gemm_resnorm,
+ *                           mirec_gemm_nn_resnorm_bwd
+ * seed_base (row tail only; device, may be NULL): when given, the launch uses
+ * key' = mix64(key ^ *seed_base), read when the kernel runs, in place of key;
+ * NULL uses key itself, so *seed_base = 0 is not the same as NULL. */
+
 /* The dropout of one launch.  All zero (or a NULL pointer) = no dropout. */
 typedef struct mirec_drop {
   float keep_prob;     /* in (0, 1]; 0 = off */
@@ -976,8 +1000,9 @@ int mirec_scatter_add_rows(const float *grad, const int32_t *ids, int64_t n,
 /* out[t] = mean over the children c in [0,k) with valid[t*k+c] >= 0 (all if
  * valid == NULL) of dropout_p-dropout(x[t*k + c]); 0 if no valid child.
  * Dropout keeps an element with probability 1-p and scales it by 1/(1-p);
- * the mask is a hash of (seed, element index), so the backward recomputes
- * it.  dim % 4 == 0. */
+ * the mask is the element dropout stated above (after mirec_edge_keep_mask)
+ * at element index (t*k + c)*dim + col, so the backward recomputes it.
+ * dim % 4 == 0. */
 int mirec_fanout_mean(const float *x, const int32_t *valid, int64_t n_targets,
                       int32_t k, int32_t dim, float dropout_p, uint64_t seed,
                       float *out, mirec_stream_t stream);
@@ -1373,9 +1398,10 @@ int mirec_gemm_tn_ex(const float *A, const float *Amask, const float *B, const f
  *         rstd = 1 / sqrt(biased var + eps)                (written if y;
  *         mean / rstd [n] then required)
  * out may be NULL only when it equals z (no res / bias / relu / dropout).
- * The dropout mask is the counter hash of (seed, row * d + col) — the same
- * seed recomputes it in the backward.  seed_base (device, may be NULL): when
- * given, *seed_base is mixed into the mask key when the kernel runs, so a
+ * The dropout mask is the element dropout stated above (after
+ * mirec_edge_keep_mask) at element index row * d + col — the same seed
+ * recomputes it in the backward.  seed_base (device, may be NULL): when
+ * given, the key becomes mix64(key ^ *seed_base) when the kernel runs, so a
  * captured HIP graph draws a fresh mask on every replay (the host writes a
  * new base before each replay; the backward reads the same base). */
 int mirec_resnorm_fwd(const float *res, const float *z, const float *bias, const float *gamma,

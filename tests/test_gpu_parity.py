@@ -3385,25 +3385,17 @@ def _tg_groups(n_rows, d, seed, hub_count=0):
 
 
 def _tg_reference(groups, n_rows, d):
-    """float64 sums of the same contributions with the kernels' dropout mask
-    (mirec_fanout_mean_gather_bwd: the float-atomic form of the leaf
-    backward) — computed as dense float64 on the host."""
-    import ctypes
-
-    from furusato_recommend_amd import _lib
+    """float64 sums of the same contributions with the dropout mask made on
+    the host (tests/dropout_common.py, the rule of include/mirec.h: no kernel
+    that shares the mask code takes part) — dense float64 on the host."""
+    from tests import dropout_common
     acc = torch.zeros(n_rows, d, dtype=torch.float64)
     for ids, gr, k, mean, p, sd in groups:
         if mean:
-            # one contribution row per entry, with the mask, via the atomic
-            # kernel on a per-entry scratch table (ids -> distinct rows)
-            n_t = ids.numel() // k
-            slots = torch.arange(ids.numel(), dtype=torch.int32, device="cuda")
-            slots = torch.where(ids >= 0, slots, torch.full_like(slots, -1))
-            per = torch.zeros(ids.numel(), d, device="cuda")
-            _lib.check(_lib.lib.mirec_fanout_mean_gather_bwd(
-                gr.data_ptr(), slots.data_ptr(), n_t, k, d, p, ctypes.c_uint64(sd),
-                per.data_ptr(), _lib.stream_handle()), "bwd")
-            per = per.cpu().double()
+            # one contribution row per entry: keep * scale * grad_out[t] / cnt_t
+            mask, scale = dropout_common.fanout_mask(p, sd, ids.numel(), d)
+            per = torch.from_numpy(dropout_common.entry_contributions(
+                gr.cpu().numpy(), ids.cpu().numpy(), k, mask, scale))
         else:
             per = gr.cpu().double()
         idc = ids.cpu().long()
