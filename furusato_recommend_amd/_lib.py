@@ -275,6 +275,15 @@ SIGNATURES = {
     "mirec_fanout_mean_gather_bwd_sorted": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                                     c_float, c_uint64, c_int32, c_void_p,
                                                     c_void_p, c_size_t, c_void_p]),
+    "mirec_fanout_gat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int64, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                                 c_void_p]),
+    "mirec_fanout_gat_bwd_work_floats": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    "mirec_fanout_gat_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int64, c_int32, c_int32, c_int32, c_float,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mirec_csr_gat": (c_int, [POINTER(CSR), c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                              c_int32, c_float, c_void_p, c_void_p, c_void_p]),
     "mirec_row_grad_group_size": (c_int64, []),
     "mirec_table_grad_workspace": (c_int, [POINTER(RowGradGroup), c_int32, c_int32, c_int32,
                                            POINTER(c_size_t)]),

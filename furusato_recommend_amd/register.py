@@ -1,6 +1,7 @@
 """Model registry with the reference's names (main.py:32-56, subset on the
 hot path: 'lgn' = LightGCN, 'lgnssm' = LightGCNSSM, 'radj' = rAdjGCN,
-'mf' = MF, 'sage' = GraphSAGE, 'sasrec' = SASRec)."""
+'mf' = MF, 'sage' = GraphSAGE, 'gnn' = GNN with conv = 'gat', 'sasrec' = SASRec)."""
+from .gnn import GNN
 from .graphsage import GraphSAGE
 from .lgcnssm import LightGCNSSM
 from .lightgcn import LightGCN
@@ -14,5 +15,6 @@ MODELS = {
     "lgnssm": LightGCNSSM,
     "radj": rAdjGCN,
     "sage": GraphSAGE,
+    "gnn": GNN,
     "sasrec": SASRec,
 }

@@ -1038,6 +1038,57 @@ int mirec_fanout_mean_gather_bwd_sorted(const float *grad_out, const int32_t *id
                                         float *table_grad, void *workspace,
                                         size_t workspace_bytes, mirec_stream_t stream);
 
+/* Graph-attention hop (PyG GATConv, concat=True, add_self_loops=True, no
+ * attention dropout; model/gnn.py:196-206) on the same fixed-fanout tree.
+ * Rows are the projected features z = x Wᵀ, D = heads * ch floats, head h
+ * the columns [h ch, (h + 1) ch).  For target t and head h, over the slots j
+ * = the children c with valid[t*k + c] >= 0 (all if valid == NULL; a repeated
+ * id counts once per slot) and the self slot, which is always present:
+ *   s_j = <z_j,h, att_src_h> + <z_t,h, att_dst_h>
+ *   e_j = s_j > 0 ? s_j : slope * s_j
+ *   alpha_j = exp(e_j - max e) / sum exp(e - max e)
+ *   out[t, h] = sum_j alpha_j z_j,h  (+ bias if not NULL)
+ * A target without a valid child gives z_self (+ bias) exactly.  alpha, if
+ * not NULL, receives [n_targets, k + 1, heads] with slot k the self slot and
+ * exactly 0 in the invalid slots.  Every child row is read once.
+ * Shapes: ch % 4 == 0, 1 <= heads <= 8, heads * ch <= 256, 1 <= k <= 64, row
+ * pointers 16-byte aligned; anything else is MIREC_ERR_ARG, nothing launched. */
+int mirec_fanout_gat(const float *z_child, const float *z_self, const int32_t *valid,
+                     const float *att_src, const float *att_dst, const float *bias,
+                     int64_t n_targets, int32_t k, int32_t heads, int32_t ch, float slope,
+                     float *out, float *alpha, mirec_stream_t stream);
+
+/* Backward of mirec_fanout_gat from the kept alpha, per head with g =
+ * grad_out[t, h]:  dalpha_j = <g, z_j>,  de_j = alpha_j (dalpha_j - sum_m
+ * alpha_m dalpha_m),  ds_j = de_j (s_j > 0 ? 1 : slope)  (s_j recomputed),
+ *   grad_z_child[t*k + c] = alpha_c g + ds_c att_src  (0 for an invalid slot)
+ *   grad_z_self[t] = alpha_self g + ds_self att_src + (sum_j ds_j) att_dst
+ *   grad_att_src = sum_t sum_j ds_j z_j,  grad_att_dst = sum_t (sum_j ds_j) z_t
+ * All four are written, not added to.  The parameter sums are per-block
+ * partial sums in work (mirec_fanout_gat_bwd_work_floats floats; -1 for a
+ * shape the kernels do not take) added in block order by a final launch: no
+ * float atomics, the same bits from run to run.  The child rows are read
+ * twice.  Same shape limits as the forward. */
+int64_t mirec_fanout_gat_bwd_work_floats(int64_t n_targets, int32_t k, int32_t heads,
+                                         int32_t ch);
+int mirec_fanout_gat_bwd(const float *grad_out, const float *z_child, const float *z_self,
+                         const int32_t *valid, const float *att_src, const float *att_dst,
+                         const float *alpha, int64_t n_targets, int32_t k, int32_t heads,
+                         int32_t ch, float slope, float *grad_z_child, float *grad_z_self,
+                         float *grad_att_src, float *grad_att_dst, float *work,
+                         mirec_stream_t stream);
+
+/* The same forward over every row of a CSR graph (full-graph inference):
+ * row r attends over its col entries (a multi-edge once per entry) and its
+ * self loop; a row without entries gives z_r (+ bias).  Reads rowptr and col
+ * only (dinv, val and the split arrays are ignored); entries outside [0,
+ * n_rows) are skipped.  logits: [n_rows, 2 * heads] scratch, written by a
+ * first launch (<z_r,h, att_src_h> then <z_r,h, att_dst_h>).  Any degree: one
+ * lane group walks a row.  heads / ch limits as mirec_fanout_gat. */
+int mirec_csr_gat(const mirec_csr_t *csr, const float *z, const float *att_src,
+                  const float *att_dst, const float *bias, int32_t heads, int32_t ch,
+                  float slope, float *out, float *logits, mirec_stream_t stream);
+
 /* Deterministic id-table gradient (model/graphsage.py:311-337) and the Adam
  * step that consumes it (graphsage.py:388-397).  The table gradient of one
  * step is G[r] = c[slice(r)] * table[r] + S[r]: c = (c_user, c_item) the
