@@ -11,6 +11,7 @@ from .dataloader import FiveCore, Loader, SyntheticBipartite  # noqa: F401
 from .graph import Graph  # noqa: F401
 from .graphsage import GraphSAGE  # noqa: F401
 from .gnn import GNN  # noqa: F401
+from .tgrec import TGRec  # noqa: F401
 from .lgconv import LGConv  # noqa: F401
 from . import ops  # noqa: F401  (registers torch.ops.mirec.*)
 from .lightgcn import LightGCN  # noqa: F401
@@ -20,5 +21,5 @@ from .radj import rAdjGCN  # noqa: F401
 from .sasrec import SASRec  # noqa: F401
 from .register import MODELS  # noqa: F401
 
-__all__ = ["LGConv", "LightGCN", "LightGCNSSM", "rAdjGCN", "MF", "GraphSAGE", "GNN", "SASRec", "Graph", "Loader", "SyntheticBipartite", "FiveCore", "MODELS",
+__all__ = ["LGConv", "LightGCN", "LightGCNSSM", "rAdjGCN", "MF", "GraphSAGE", "GNN", "TGRec", "SASRec", "Graph", "Loader", "SyntheticBipartite", "FiveCore", "MODELS",
            "MirecError", "LIB_PATH"]

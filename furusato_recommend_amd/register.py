@@ -1,6 +1,7 @@
 """Model registry with the reference's names (main.py:32-56, subset on the
 hot path: 'lgn' = LightGCN, 'lgnssm' = LightGCNSSM, 'radj' = rAdjGCN,
-'mf' = MF, 'sage' = GraphSAGE, 'gnn' = GNN with conv = 'gat', 'sasrec' = SASRec)."""
+'mf' = MF, 'sage' = GraphSAGE, 'gnn' = GNN with conv = 'gat', 'tgrec' = TGRec
+(TransformerConv hops), 'sasrec' = SASRec)."""
 from .gnn import GNN
 from .graphsage import GraphSAGE
 from .lgcnssm import LightGCNSSM
@@ -8,6 +9,7 @@ from .lightgcn import LightGCN
 from .mf import MF
 from .radj import rAdjGCN
 from .sasrec import SASRec
+from .tgrec import TGRec
 
 MODELS = {
     "mf": MF,
@@ -16,5 +18,6 @@ MODELS = {
     "radj": rAdjGCN,
     "sage": GraphSAGE,
     "gnn": GNN,
+    "tgrec": TGRec,
     "sasrec": SASRec,
 }

@@ -1089,6 +1089,64 @@ int mirec_csr_gat(const mirec_csr_t *csr, const float *z, const float *att_src,
                   const float *att_dst, const float *bias, int32_t heads, int32_t ch,
                   float slope, float *out, float *logits, mirec_stream_t stream);
 
+/* Dot-product attention hop (PyG TransformerConv, concat=True, beta=False, no
+ * edge features, no attention dropout, root_weight=True; model/tgrec.py:
+ * 161-171) on the same fixed-fanout tree.  Rows are projected features of D =
+ * heads * ch floats, head h the columns [h ch, (h + 1) ch): query / skip rows
+ * of the targets at stride ld_q, key / value rows of the children at stride
+ * ld_kv (strides in floats, so q | skip and k | v may be the halves of one
+ * [n, 2D] GEMM output).  For target t and head h, over the slots j = the
+ * children c with valid[t*k + c] >= 0 (all if valid == NULL; a repeated id
+ * counts once per slot; there is NO self slot):
+ *   s_j = <query[t],h, key[t*k + j],h> * scale
+ *   alpha_j = exp(s_j - max s) / sum exp(s - max s)
+ *   out[t, h] = sum_j alpha_j value[t*k + j],h  (+ skip[t],h if skip != NULL)
+ * A target without a valid child gives its skip row exactly as stored (zeros
+ * without skip) and alpha slots of exactly 0.  out is contiguous [n_targets,
+ * D]; alpha, if not NULL, receives [n_targets, k, heads] with exactly 0 in
+ * the invalid slots.  Every key row and every value row is read once.
+ * Shapes: ch % 4 == 0, 1 <= heads <= 8, heads * ch <= 256, 1 <= k <= 64,
+ * every stride >= D and a multiple of 4, every pointer 16-byte aligned,
+ * scale not NaN; anything else is MIREC_ERR_ARG, nothing launched (checked
+ * before any device call).  n_targets == 0 is MIREC_OK.  The rows must be
+ * finite and their logits too: a logit of -inf (a dot that overflowed) has
+ * weight 0, and a target whose valid slots all have it divides 0 by 0. */
+int mirec_fanout_tattn(const float *query, const float *skip, int64_t ld_q,
+                       const float *key, const float *value, int64_t ld_kv,
+                       const int32_t *valid, int64_t n_targets, int32_t k,
+                       int32_t heads, int32_t ch, float scale,
+                       float *out, float *alpha, mirec_stream_t stream);
+
+/* Backward of mirec_fanout_tattn from the kept alpha [n_targets, k, heads],
+ * per head with g = grad_out[t, h] (grad_out contiguous [n_targets, D]):
+ *   dalpha_j = <g, value_j>,  ds_j = alpha_j (dalpha_j - sum_m alpha_m dalpha_m)
+ *   grad_value[t*k + j] = alpha_j g          (0 for an invalid slot)
+ *   grad_key[t*k + j]   = ds_j scale query[t] (0 for an invalid slot)
+ *   grad_query[t] = sum_j ds_j scale key[t*k + j]
+ *   grad_skip[t]  = g                         (if grad_skip != NULL)
+ * grad_query / grad_skip rows lie at stride ld_gq, grad_key / grad_value rows
+ * at stride ld_gkv.  Every child row has one parent, so all four are plain
+ * stores: written, not added to; no atomics, no workspace, the same bits from
+ * run to run.  The value rows are read twice, the key rows once.  Same shape,
+ * stride and alignment limits as the forward. */
+int mirec_fanout_tattn_bwd(const float *grad_out, const float *query, int64_t ld_q,
+                           const float *key, const float *value, int64_t ld_kv,
+                           const int32_t *valid, const float *alpha,
+                           int64_t n_targets, int32_t k, int32_t heads, int32_t ch, float scale,
+                           float *grad_query, float *grad_skip, int64_t ld_gq,
+                           float *grad_key, float *grad_value, int64_t ld_gkv,
+                           mirec_stream_t stream);
+
+/* The same forward over every row of a CSR graph (full-graph inference): row
+ * r attends with query[r] over the key / value rows of its col entries (a
+ * multi-edge once per entry; no self loop); a row without entries gives its
+ * skip row.  query / skip / key / value hold one row per graph row.  Reads
+ * rowptr and col only; entries outside [0, n_rows) are skipped.  Any degree:
+ * one lane group walks a row.  Limits as mirec_fanout_tattn. */
+int mirec_csr_tattn(const mirec_csr_t *csr, const float *query, const float *skip, int64_t ld_q,
+                    const float *key, const float *value, int64_t ld_kv,
+                    int32_t heads, int32_t ch, float scale, float *out, mirec_stream_t stream);
+
 /* Deterministic id-table gradient (model/graphsage.py:311-337) and the Adam
  * step that consumes it (graphsage.py:388-397).  The table gradient of one
  * step is G[r] = c[slice(r)] * table[r] + S[r]: c = (c_user, c_item) the
