@@ -11,19 +11,17 @@
 //   mirec_fanout_gat_bwd  ∂z_child, ∂z_self, ∂att_src, ∂att_dst from alpha
 //   mirec_csr_gat         forward over every CSR row (full-graph inference)
 //
-// Layout.  A row of D = H·C floats is D/4 float4 columns; a target is owned
-// by a group of LPT = 2^lg >= D/4 consecutive lanes (64 / LPT targets per
-// wave, lanes past D/4 idle), lane `sub` holding columns 4 sub .. 4 sub + 3,
-// all of head sub / (C/4) because C % 4 == 0.  A head's dot is summed inside
-// the C/4 lanes that own it: an xor butterfly when C/4 is a power of two
-// (the head groups are then aligned), else every lane adds its head's lanes
-// in lane order — both fixed orders.
+// Layout: headrow.h's (shared with tattn.hip) — one group of lanes per
+// target, a float4 column per lane, a head's dot summed inside the lanes that
+// own it.
 //
 // Forward: every child row is read once.  The running (max, sum, acc) of an
 // online softmax starts from the self slot (max = e_self, sum = 1, acc =
 // z_self), so the maximum is finite from the start and a target without a
 // valid child leaves z_self untouched (no division).  Children come in
-// batches of 8: flags, then 8 rows in flight, one rescale per batch.  When
+// batches of 8: flags, then 8 rows in flight, one rescale per batch — the
+// step headrow.h has as softmax_fold, written out in the two forward kernels
+// here because they measured slower with the call.  When
 // alpha is kept the raw e_j go to the alpha buffer and the lane that wrote
 // them normalises them in place once the final (max, sum) is known.
 // Exponentials are exp2 of the log2(e)-scaled argument (common.h).
@@ -42,48 +40,11 @@
 // shape alone), the block adds its groups in group order into `work`, and a
 // final launch adds the blocks' partials in block order: no float atomics,
 // bitwise the same from run to run.
-#include "common.h"
+#include "headrow.h"
 
 namespace mirec {
 
-constexpr int kGatBatch = 8;
 constexpr int kGatMaxBlocks = 1024;  // partial sums of the backward
-
-struct GatLane {
-  int sub;    // float4 column of this lane inside its target group
-  int h;      // its head (0 for an idle lane)
-  int hb;     // wave lane of the head's first lane
-  bool col;   // sub < D/4
-  bool lead;  // first lane of its head
-};
-
-__device__ __forceinline__ GatLane gat_lane(int lg, int d4, int g) {
-  GatLane L;
-  const int lane = threadIdx.x & 63;
-  L.sub = lane & ((1 << lg) - 1);
-  L.col = L.sub < d4;
-  L.h = L.col ? L.sub / g : 0;
-  L.hb = (lane - L.sub) + L.h * g;
-  L.lead = L.col && L.sub == L.h * g;
-  return L;
-}
-
-// Sum of v over the g lanes of the caller's head (every lane of the wave
-// calls; idle lanes pass 0).
-template <bool POW2>
-__device__ __forceinline__ float head_sum(float v, int g, int hb) {
-  if (POW2) {
-    for (int m = 1; m < g; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-  }
-  float s = 0.f;
-  for (int j = 0; j < g; ++j) s += __shfl(v, hb + j);
-  return s;
-}
-
-__device__ __forceinline__ float f4_dotf(float4 a, float4 b) {
-  return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
-}
 
 __device__ __forceinline__ float leaky(float s, float slope) { return s > 0.f ? s : slope * s; }
 
@@ -93,7 +54,7 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void fanout_gat_kernel(
     const float *__restrict__ att_src, const float *__restrict__ att_dst,
     const float *__restrict__ bias, int64_t n_t, int32_t k, int32_t heads, int32_t d4, int32_t g,
     int32_t lg, float slope, float *__restrict__ out, float *alpha) {
-  const GatLane L = gat_lane(lg, d4, g);
+  const HeadLane L = head_lane(lg, d4, g);
   const int64_t t = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> lg;
   const bool live = t < n_t;
   const bool act = live && L.col;
@@ -101,27 +62,30 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void fanout_gat_kernel(
   const float4 a_s = L.col ? ld4(att_src + 4 * L.sub) : f4_zero();
   const float4 a_d = L.col ? ld4(att_dst + 4 * L.sub) : f4_zero();
   const float4 zself = act ? ld4(zs + t * D + 4 * L.sub) : f4_zero();
-  const float sd = head_sum<POW2>(f4_dotf(zself, a_d), g, L.hb);
-  const float e_self = leaky(head_sum<POW2>(f4_dotf(zself, a_s), g, L.hb) + sd, slope);
+  const float sd = head_sum<POW2>(f4_dot_fma(zself, a_d), g, L.hb);
+  const float e_self = leaky(head_sum<POW2>(f4_dot_fma(zself, a_s), g, L.hb) + sd, slope);
   float m = e_self, l = 1.f;
   float4 acc = zself;
   bool any = false;
   const bool keep_a = alpha != nullptr && live && L.lead;
   float *arow = alpha != nullptr && live ? alpha + (t * (k + 1)) * heads + L.h : nullptr;
-  for (int c0 = 0; c0 < k; c0 += kGatBatch) {
-    bool ok[kGatBatch];
+  for (int c0 = 0; c0 < k; c0 += kHeadBatch) {
+    bool ok[kHeadBatch];
 #pragma unroll
-    for (int u = 0; u < kGatBatch; ++u)
+    for (int u = 0; u < kHeadBatch; ++u)
       ok[u] = live && c0 + u < k && (valid == nullptr || valid[t * k + c0 + u] >= 0);
-    float4 v[kGatBatch];
+    float4 v[kHeadBatch];
 #pragma unroll
-    for (int u = 0; u < kGatBatch; ++u)
+    for (int u = 0; u < kHeadBatch; ++u)
       v[u] = (act && ok[u]) ? ld4(zc + (t * k + c0 + u) * D + 4 * L.sub) : f4_zero();
-    float e[kGatBatch];
+    // headrow.h's softmax_fold, inline: with the fold as a call (and the
+    // alpha store beside it) two of the three measured shapes ran slower
+    // 
+    float e[kHeadBatch];
     float mb = m;
 #pragma unroll
-    for (int u = 0; u < kGatBatch; ++u) {
-      e[u] = leaky(head_sum<POW2>(f4_dotf(v[u], a_s), g, L.hb) + sd, slope);
+    for (int u = 0; u < kHeadBatch; ++u) {
+      e[u] = leaky(head_sum<POW2>(f4_dot_fma(v[u], a_s), g, L.hb) + sd, slope);
       if (ok[u]) mb = fmaxf(mb, e[u]);
     }
     const float r = exp2_hw((m - mb) * kLog2e);  // 1 when the maximum stays
@@ -129,7 +93,7 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void fanout_gat_kernel(
     acc = f4_scale(r, acc);
     m = mb;
 #pragma unroll
-    for (int u = 0; u < kGatBatch; ++u) {
+    for (int u = 0; u < kHeadBatch; ++u) {
       if (ok[u]) {
         const float p = exp2_hw((e[u] - mb) * kLog2e);
         l += p;
@@ -166,7 +130,7 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void fanout_gat_bwd_kernel(
     int32_t g, int32_t lg, float slope, float *__restrict__ gzc, float *__restrict__ gzs,
     float *__restrict__ work) {
   __shared__ float4 red[2][256];
-  const GatLane L = gat_lane(lg, d4, g);
+  const HeadLane L = head_lane(lg, d4, g);
   const int gpb = 256 >> lg;  // targets per block and round
   const int64_t D = (int64_t)d4 * 4;
   const float4 a_s = L.col ? ld4(att_src + 4 * L.sub) : f4_zero();
@@ -179,42 +143,42 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void fanout_gat_bwd_kernel(
     const float4 gg = act ? ld4(grad_out + t * D + 4 * L.sub) : f4_zero();
     const float4 zself = act ? ld4(zs + t * D + 4 * L.sub) : f4_zero();
     const float *arow = alpha + (t * (k + 1)) * heads + L.h;
-    const float sd = head_sum<POW2>(f4_dotf(zself, a_d), g, L.hb);
-    const float s_self = head_sum<POW2>(f4_dotf(zself, a_s), g, L.hb) + sd;
-    const float da_self = head_sum<POW2>(f4_dotf(gg, zself), g, L.hb);
+    const float sd = head_sum<POW2>(f4_dot_fma(zself, a_d), g, L.hb);
+    const float s_self = head_sum<POW2>(f4_dot_fma(zself, a_s), g, L.hb) + sd;
+    const float da_self = head_sum<POW2>(f4_dot_fma(gg, zself), g, L.hb);
     const float al_self = live ? arow[(int64_t)k * heads] : 0.f;
     // pass 1: S = Σ_m alpha_m dalpha_m (children in slot order, then self)
     double S = 0.0;
-    for (int c0 = 0; c0 < k; c0 += kGatBatch) {
-      float al[kGatBatch];
-      float4 v[kGatBatch];
+    for (int c0 = 0; c0 < k; c0 += kHeadBatch) {
+      float al[kHeadBatch];
+      float4 v[kHeadBatch];
 #pragma unroll
-      for (int u = 0; u < kGatBatch; ++u) {
+      for (int u = 0; u < kHeadBatch; ++u) {
         const bool ok = live && c0 + u < k && (valid == nullptr || valid[t * k + c0 + u] >= 0);
         al[u] = ok ? arow[(int64_t)(c0 + u) * heads] : 0.f;
         v[u] = (act && ok) ? ld4(zc + (t * k + c0 + u) * D + 4 * L.sub) : f4_zero();
       }
 #pragma unroll
-      for (int u = 0; u < kGatBatch; ++u)
-        S = fma((double)al[u], (double)head_sum<POW2>(f4_dotf(gg, v[u]), g, L.hb), S);
+      for (int u = 0; u < kHeadBatch; ++u)
+        S = fma((double)al[u], (double)head_sum<POW2>(f4_dot_fma(gg, v[u]), g, L.hb), S);
     }
     S = fma((double)al_self, (double)da_self, S);
     // pass 2: ds_j, ∂z_j, and this lane's columns of the parameter sums
     double sum_dsd = 0.0;
-    for (int c0 = 0; c0 < k; c0 += kGatBatch) {
-      float al[kGatBatch];
-      float4 v[kGatBatch];
-      bool ok[kGatBatch];
+    for (int c0 = 0; c0 < k; c0 += kHeadBatch) {
+      float al[kHeadBatch];
+      float4 v[kHeadBatch];
+      bool ok[kHeadBatch];
 #pragma unroll
-      for (int u = 0; u < kGatBatch; ++u) {
+      for (int u = 0; u < kHeadBatch; ++u) {
         ok[u] = live && c0 + u < k && (valid == nullptr || valid[t * k + c0 + u] >= 0);
         al[u] = ok[u] ? arow[(int64_t)(c0 + u) * heads] : 0.f;
         v[u] = (act && ok[u]) ? ld4(zc + (t * k + c0 + u) * D + 4 * L.sub) : f4_zero();
       }
 #pragma unroll
-      for (int u = 0; u < kGatBatch; ++u) {
-        const float da = head_sum<POW2>(f4_dotf(gg, v[u]), g, L.hb);
-        const float s = head_sum<POW2>(f4_dotf(v[u], a_s), g, L.hb) + sd;
+      for (int u = 0; u < kHeadBatch; ++u) {
+        const float da = head_sum<POW2>(f4_dot_fma(gg, v[u]), g, L.hb);
+        const float s = head_sum<POW2>(f4_dot_fma(v[u], a_s), g, L.hb) + sd;
         const double dsd =
             ok[u] ? (double)al[u] * ((double)da - S) * (s > 0.f ? 1.0 : (double)slope) : 0.0;
         sum_dsd += dsd;
@@ -271,14 +235,14 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void csr_gat_logits_kernel(
     const float *__restrict__ z, const float *__restrict__ att_src,
     const float *__restrict__ att_dst, int64_t n_rows, int32_t heads, int32_t d4, int32_t g,
     int32_t lg, float *__restrict__ logits) {
-  const GatLane L = gat_lane(lg, d4, g);
+  const HeadLane L = head_lane(lg, d4, g);
   const int64_t r = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> lg;
   const bool act = r < n_rows && L.col;
   const float4 x = act ? ld4(z + r * d4 * 4 + 4 * L.sub) : f4_zero();
   const float4 a_s = L.col ? ld4(att_src + 4 * L.sub) : f4_zero();
   const float4 a_d = L.col ? ld4(att_dst + 4 * L.sub) : f4_zero();
-  const float ss = head_sum<POW2>(f4_dotf(x, a_s), g, L.hb);
-  const float sd = head_sum<POW2>(f4_dotf(x, a_d), g, L.hb);
+  const float ss = head_sum<POW2>(f4_dot_fma(x, a_s), g, L.hb);
+  const float sd = head_sum<POW2>(f4_dot_fma(x, a_d), g, L.hb);
   if (r < n_rows && L.lead) {
     logits[r * 2 * heads + L.h] = ss;
     logits[r * 2 * heads + heads + L.h] = sd;
@@ -294,7 +258,7 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void csr_gat_kernel(
     const float *__restrict__ z, const float *__restrict__ logits,
     const float *__restrict__ bias, int64_t n_rows, int32_t heads, int32_t d4, int32_t g,
     int32_t lg, float slope, float *__restrict__ out) {
-  const GatLane L = gat_lane(lg, d4, g);
+  const HeadLane L = head_lane(lg, d4, g);
   const int64_t r = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> lg;
   if (r >= n_rows || !L.col) return;  // no lane exchange below
   const int64_t D = (int64_t)d4 * 4;
@@ -304,22 +268,24 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void csr_gat_kernel(
   float m = leaky(logits[r * H2 + L.h] + sd, slope), l = 1.f;
   float4 acc = zself;
   const int64_t beg = rowptr[r], end = rowptr[r + 1];
-  for (int64_t j0 = beg; j0 < end; j0 += kGatBatch) {
-    int32_t src[kGatBatch];
+  for (int64_t j0 = beg; j0 < end; j0 += kHeadBatch) {
+    int32_t src[kHeadBatch];
 #pragma unroll
-    for (int u = 0; u < kGatBatch; ++u) src[u] = j0 + u < end ? col[j0 + u] : -1;
-    float e[kGatBatch];
-    float4 v[kGatBatch];
+    for (int u = 0; u < kHeadBatch; ++u) src[u] = j0 + u < end ? col[j0 + u] : -1;
+    float e[kHeadBatch];
+    float4 v[kHeadBatch];
 #pragma unroll
-    for (int u = 0; u < kGatBatch; ++u) {
+    for (int u = 0; u < kHeadBatch; ++u) {
       const bool ok = src[u] >= 0 && src[u] < n_rows;
       e[u] = ok ? logits[(int64_t)src[u] * H2 + L.h] : 0.f;
       v[u] = ok ? ld4(z + (int64_t)src[u] * D + 4 * L.sub) : f4_zero();
       if (!ok) src[u] = -1;
     }
+    // headrow.h's softmax_fold, inline (the valid flag is src[u] >= 0): as a
+    // call it measured slower
     float mb = m;
 #pragma unroll
-    for (int u = 0; u < kGatBatch; ++u) {
+    for (int u = 0; u < kHeadBatch; ++u) {
       e[u] = leaky(e[u] + sd, slope);
       if (src[u] >= 0) mb = fmaxf(mb, e[u]);
     }
@@ -328,7 +294,7 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void csr_gat_kernel(
     acc = f4_scale(rs, acc);
     m = mb;
 #pragma unroll
-    for (int u = 0; u < kGatBatch; ++u) {
+    for (int u = 0; u < kHeadBatch; ++u) {
       if (src[u] >= 0) {
         const float p = exp2_hw((e[u] - mb) * kLog2e);
         l += p;
@@ -341,16 +307,8 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void csr_gat_kernel(
   st4(out + r * D + 4 * L.sub, o);
 }
 
-static bool gat_shape_ok(int32_t k, int32_t heads, int32_t ch) {
-  return heads >= 1 && heads <= 8 && ch >= 4 && ch % 4 == 0 && heads * ch <= 256 && k >= 1 &&
-         k <= 64;
-}
-
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 static int gat_bwd_blocks(int64_t n_targets, int lg) {
-  const int64_t gpb = 256 >> lg;
-  const int64_t b = (n_targets + gpb - 1) / gpb;
+  const int64_t b = head_blocks(n_targets, lg);
   return (int)(b < kGatMaxBlocks ? b : kGatMaxBlocks);
 }
 
@@ -361,31 +319,23 @@ extern "C" int mirec_fanout_gat(const float *z_child, const float *z_self, const
                                 int64_t n_targets, int32_t k, int32_t heads, int32_t ch,
                                 float slope, float *out, float *alpha, mirec_stream_t stream) {
   using namespace mirec;
-  MIREC_CHECK_ARG(n_targets >= 0 && gat_shape_ok(k, heads, ch) && slope == slope);
+  MIREC_CHECK_ARG(n_targets >= 0 && head_shape_ok(k, heads, ch) && slope == slope);
   if (n_targets == 0) return MIREC_OK;
   MIREC_CHECK_ARG(z_child && z_self && att_src && att_dst && out);
   MIREC_CHECK_ARG(aligned16(z_child) && aligned16(z_self) && aligned16(att_src) &&
                   aligned16(att_dst) && aligned16(bias) && aligned16(out));
   const int d4 = heads * ch / 4, g = ch / 4, lg = row_lg(d4);
-  const int64_t blocks = (n_targets + (256 >> lg) - 1) / (256 >> lg);
-  MIREC_CHECK_ARG(blocks < ((int64_t)1 << 31));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if ((g & (g - 1)) == 0)
-    hipLaunchKernelGGL(fanout_gat_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, z_child,
-                       z_self, valid, att_src, att_dst, bias, n_targets, k, heads, d4, g, lg,
-                       slope, out, alpha);
-  else
-    hipLaunchKernelGGL(fanout_gat_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st,
-                       z_child, z_self, valid, att_src, att_dst, bias, n_targets, k, heads, d4, g,
-                       lg, slope, out, alpha);
-  MIREC_LAUNCH_CHECK();
+  MIREC_HEADROW_LAUNCH(fanout_gat_kernel, head_blocks(n_targets, lg), g, st, z_child, z_self,
+                       valid, att_src, att_dst, bias, n_targets, k, heads, d4, g, lg, slope, out,
+                       alpha);
   return MIREC_OK;
 }
 
 extern "C" int64_t mirec_fanout_gat_bwd_work_floats(int64_t n_targets, int32_t k, int32_t heads,
                                                     int32_t ch) {
   using namespace mirec;
-  if (n_targets < 0 || !gat_shape_ok(k, heads, ch)) return -1;
+  if (n_targets < 0 || !head_shape_ok(k, heads, ch)) return -1;
   const int d4 = heads * ch / 4;
   return (int64_t)gat_bwd_blocks(n_targets, row_lg(d4)) * 2 * d4 * 4;
 }
@@ -398,7 +348,7 @@ extern "C" int mirec_fanout_gat_bwd(const float *grad_out, const float *z_child,
                                     float *grad_z_self, float *grad_att_src, float *grad_att_dst,
                                     float *work, mirec_stream_t stream) {
   using namespace mirec;
-  MIREC_CHECK_ARG(n_targets >= 0 && gat_shape_ok(k, heads, ch) && slope == slope);
+  MIREC_CHECK_ARG(n_targets >= 0 && head_shape_ok(k, heads, ch) && slope == slope);
   MIREC_CHECK_ARG(grad_att_src && grad_att_dst);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int D = heads * ch, d4 = D / 4, g = ch / 4, lg = row_lg(d4);
@@ -413,15 +363,9 @@ extern "C" int mirec_fanout_gat_bwd(const float *grad_out, const float *z_child,
                   aligned16(att_src) && aligned16(att_dst) && aligned16(grad_z_child) &&
                   aligned16(grad_z_self) && aligned16(work));
   const int blocks = gat_bwd_blocks(n_targets, lg);
-  if ((g & (g - 1)) == 0)
-    hipLaunchKernelGGL(fanout_gat_bwd_kernel<true>, dim3(blocks), dim3(256), 0, st, grad_out,
-                       z_child, z_self, valid, att_src, att_dst, alpha, n_targets, k, heads, d4, g,
-                       lg, slope, grad_z_child, grad_z_self, work);
-  else
-    hipLaunchKernelGGL(fanout_gat_bwd_kernel<false>, dim3(blocks), dim3(256), 0, st, grad_out,
-                       z_child, z_self, valid, att_src, att_dst, alpha, n_targets, k, heads, d4, g,
-                       lg, slope, grad_z_child, grad_z_self, work);
-  MIREC_LAUNCH_CHECK();
+  MIREC_HEADROW_LAUNCH(fanout_gat_bwd_kernel, blocks, g, st, grad_out, z_child, z_self, valid,
+                       att_src, att_dst, alpha, n_targets, k, heads, d4, g, lg, slope,
+                       grad_z_child, grad_z_self, work);
   hipLaunchKernelGGL(gat_param_sum_kernel, dim3((2 * D + 3) / 4), dim3(256), 0, st, work, blocks,
                      D, grad_att_src, grad_att_dst);
   MIREC_LAUNCH_CHECK();
@@ -432,22 +376,16 @@ extern "C" int mirec_csr_gat(const mirec_csr_t *csr, const float *z, const float
                              const float *att_dst, const float *bias, int32_t heads, int32_t ch,
                              float slope, float *out, float *logits, mirec_stream_t stream) {
   using namespace mirec;
-  MIREC_CHECK_ARG(csr && csr->n_rows >= 0 && gat_shape_ok(1, heads, ch) && slope == slope);
+  MIREC_CHECK_ARG(csr && csr->n_rows >= 0 && head_shape_ok(1, heads, ch) && slope == slope);
   if (csr->n_rows == 0) return MIREC_OK;
   MIREC_CHECK_ARG(csr->rowptr && csr->col && z && att_src && att_dst && out && logits);
   MIREC_CHECK_ARG(aligned16(z) && aligned16(att_src) && aligned16(att_dst) && aligned16(bias) &&
                   aligned16(out));
   const int d4 = heads * ch / 4, g = ch / 4, lg = row_lg(d4);
-  const int64_t blocks = (csr->n_rows + (256 >> lg) - 1) / (256 >> lg);
-  MIREC_CHECK_ARG(blocks < ((int64_t)1 << 31));
+  const int64_t blocks = head_blocks(csr->n_rows, lg);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if ((g & (g - 1)) == 0)
-    hipLaunchKernelGGL(csr_gat_logits_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, z,
-                       att_src, att_dst, csr->n_rows, heads, d4, g, lg, logits);
-  else
-    hipLaunchKernelGGL(csr_gat_logits_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, z,
-                       att_src, att_dst, csr->n_rows, heads, d4, g, lg, logits);
-  MIREC_LAUNCH_CHECK();
+  MIREC_HEADROW_LAUNCH(csr_gat_logits_kernel, blocks, g, st, z, att_src, att_dst, csr->n_rows,
+                       heads, d4, g, lg, logits);
   hipLaunchKernelGGL(csr_gat_kernel, dim3((unsigned)blocks), dim3(256), 0, st, csr->rowptr,
                      csr->col, z, logits, bias, csr->n_rows, heads, d4, g, lg, slope, out);
   MIREC_LAUNCH_CHECK();

@@ -16,22 +16,17 @@
 // the two halves of one [n, 2D] GEMM output (and the gradients the two halves
 // of the buffer the GEMM's backward reads): no copy either way.
 //
-// Layout: gat.hip's.  A row of D = H·C floats is D/4 float4 columns; a target
-// is owned by LPT = 2^lg >= D/4 consecutive lanes, lane `sub` holding columns
-// 4 sub .. 4 sub + 3, all of head sub / (C/4).  A head's dot is summed inside
-// the C/4 lanes that own it: an xor butterfly when C/4 is a power of two,
-// else every lane adds its head's lanes in lane order — both fixed orders.
+// Layout: headrow.h's (shared with gat.hip) — one group of lanes per target,
+// a float4 column per lane, a head's dot summed inside the lanes that own it.
 //
 // Forward: every k row and every v row is read once.  There is no self slot
-// to seed the online softmax, so the running maximum starts at -FLT_MAX (a
-// finite number: the first rescale is exp2 of a large negative argument, 0,
-// times l = 0 and acc = 0, never inf - inf) and a target without a valid
-// child is decided by a flag, not by a division: it gets its skip row as
-// loaded, bit for bit, and alpha slots of exactly 0.  Children come in
-// batches of 8: flags, then 8 k rows and 8 v rows in flight, the 8 head
-// dots, one rescale per batch.  When alpha is kept the raw s_j go to the
-// alpha buffer and the lane that wrote them normalises them in place once the
-// final (max, sum) is known.
+// to seed the online softmax, so it starts empty (headrow.h, softmax_empty)
+// and a target without a valid child is decided by the state's flag, not by
+// a division: it gets its skip row as loaded, bit for bit, and alpha slots
+// of exactly 0.  Children come in batches of 8: flags, then 8 k rows and 8 v
+// rows in flight, the 8 head dots, one rescale per batch.  When alpha is kept
+// the raw s_j go to the alpha buffer and the lane that wrote them normalises
+// them in place once the final (max, sum) is known.
 //
 // Backward: two passes over a target's v rows (the second one a cache hit),
 // one over its k rows.  Pass 1 reads v_j and sums S = Σ_m alpha_m dalpha_m,
@@ -44,89 +39,13 @@
 // cancels exactly (gat.hip).  Every child row has one
 // parent, so all four outputs are plain stores: no atomics, no partial sums,
 // no workspace, one lane group per target and no grid-stride loop.
-#include <float.h>
-
-#include "common.h"
+#include "headrow.h"
 
 namespace mirec {
 
-constexpr int kTatBatch = 8;
-
-struct TatLane {
-  int sub;    // float4 column of this lane inside its target group
-  int h;      // its head (0 for an idle lane)
-  int hb;     // wave lane of the head's first lane
-  bool col;   // sub < D/4
-  bool lead;  // first lane of its head
-};
-
-__device__ __forceinline__ TatLane tat_lane(int lg, int d4, int g) {
-  TatLane L;
-  const int lane = threadIdx.x & 63;
-  L.sub = lane & ((1 << lg) - 1);
-  L.col = L.sub < d4;
-  L.h = L.col ? L.sub / g : 0;
-  L.hb = (lane - L.sub) + L.h * g;
-  L.lead = L.col && L.sub == L.h * g;
-  return L;
-}
-
-// Sum of v over the g lanes of the caller's head (every lane that can reach
-// the call calls it; idle lanes pass 0 and are read by nobody).
-template <bool POW2>
-__device__ __forceinline__ float tat_head_sum(float v, int g, int hb) {
-  if (POW2) {
-    for (int m = 1; m < g; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-  }
-  float s = 0.f;
-  for (int j = 0; j < g; ++j) s += __shfl(v, hb + j);
-  return s;
-}
-
-__device__ __forceinline__ float tat_dot(float4 a, float4 b) {
-  return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
-}
-
-// The running state of one lane's online softmax and the step that folds a
-// batch of up to 8 (logit, value row) pairs into it.
-struct TatState {
-  float m, l;
-  float4 acc;
-  bool any;
-};
-
-__device__ __forceinline__ TatState tat_init() {
-  return TatState{-FLT_MAX, 0.f, f4_zero(), false};
-}
-
-__device__ __forceinline__ void tat_fold(TatState &S, const float (&s)[kTatBatch],
-                                         const float4 (&v)[kTatBatch],
-                                         const bool (&ok)[kTatBatch]) {
-  float mb = S.m;
-#pragma unroll
-  for (int u = 0; u < kTatBatch; ++u)
-    if (ok[u]) mb = fmaxf(mb, s[u]);
-  // 1 when the maximum stays; 0 (times l = 0, acc = 0) on the first batch
-  // with a valid child, where m is still -FLT_MAX
-  const float r = exp2_hw((S.m - mb) * kLog2e);
-  S.l *= r;
-  S.acc = f4_scale(r, S.acc);
-  S.m = mb;
-#pragma unroll
-  for (int u = 0; u < kTatBatch; ++u) {
-    if (ok[u]) {
-      const float p = exp2_hw((s[u] - mb) * kLog2e);
-      S.l += p;
-      S.acc = f4_fma(p, v[u], S.acc);
-      S.any = true;
-    }
-  }
-}
-
 // out row of a finished state: the aggregate (none for a childless target:
 // no division) plus the skip row, which a childless target gets as loaded.
-__device__ __forceinline__ void tat_store(const TatState &S, const float *skip_row,
+__device__ __forceinline__ void tat_store(const SoftmaxState &S, const float *skip_row,
                                           float *out_row) {
   float4 o = S.any ? f4_scale(1.f / S.l, S.acc) : f4_zero();
   if (skip_row != nullptr) {
@@ -142,34 +61,34 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void fanout_tattn_kernel(
     const float *__restrict__ key, const float *__restrict__ val, int64_t ld_kv,
     const int32_t *__restrict__ valid, int64_t n_t, int32_t k, int32_t heads, int32_t d4,
     int32_t g, int32_t lg, float scale, float *__restrict__ out, float *alpha) {
-  const TatLane L = tat_lane(lg, d4, g);
+  const HeadLane L = head_lane(lg, d4, g);
   const int64_t t = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> lg;
   const bool live = t < n_t;
   const bool act = live && L.col;
   const int64_t D = (int64_t)d4 * 4;
   const float4 qv = act ? ld4(q + t * ld_q + 4 * L.sub) : f4_zero();
-  TatState S = tat_init();
+  SoftmaxState S = softmax_empty();
   const bool keep_a = alpha != nullptr && live && L.lead;
   float *arow = alpha != nullptr && live ? alpha + (t * k) * heads + L.h : nullptr;
-  for (int c0 = 0; c0 < k; c0 += kTatBatch) {
-    bool ok[kTatBatch];
+  for (int c0 = 0; c0 < k; c0 += kHeadBatch) {
+    bool ok[kHeadBatch];
 #pragma unroll
-    for (int u = 0; u < kTatBatch; ++u)
+    for (int u = 0; u < kHeadBatch; ++u)
       ok[u] = live && c0 + u < k && (valid == nullptr || valid[t * k + c0 + u] >= 0);
-    float4 kr[kTatBatch], vr[kTatBatch];
+    float4 kr[kHeadBatch], vr[kHeadBatch];
 #pragma unroll
-    for (int u = 0; u < kTatBatch; ++u) {
+    for (int u = 0; u < kHeadBatch; ++u) {
       const int64_t off = (t * k + c0 + u) * ld_kv + 4 * L.sub;
       kr[u] = (act && ok[u]) ? ld4(key + off) : f4_zero();
       vr[u] = (act && ok[u]) ? ld4(val + off) : f4_zero();
     }
-    float s[kTatBatch];
+    float s[kHeadBatch];
 #pragma unroll
-    for (int u = 0; u < kTatBatch; ++u) {
-      s[u] = tat_head_sum<POW2>(tat_dot(qv, kr[u]), g, L.hb) * scale;
+    for (int u = 0; u < kHeadBatch; ++u) {
+      s[u] = head_sum<POW2>(f4_dot_fma(qv, kr[u]), g, L.hb) * scale;
       if (keep_a && c0 + u < k) arow[(int64_t)(c0 + u) * heads] = ok[u] ? s[u] : 0.f;
     }
-    tat_fold(S, s, vr, ok);
+    softmax_fold(S, s, vr, ok);
   }
   if (act)
     tat_store(S, skip != nullptr ? skip + t * ld_q + 4 * L.sub : nullptr, out + t * D + 4 * L.sub);
@@ -191,7 +110,7 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void fanout_tattn_bwd_kernel(
     int32_t heads, int32_t d4, int32_t g, int32_t lg, float scale, float *__restrict__ gq,
     float *__restrict__ gskip, int64_t ld_gq, float *__restrict__ gk, float *__restrict__ gv,
     int64_t ld_gkv) {
-  const TatLane L = tat_lane(lg, d4, g);
+  const HeadLane L = head_lane(lg, d4, g);
   const int64_t t = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> lg;
   const bool live = t < n_t;
   const bool act = live && L.col;
@@ -201,27 +120,27 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void fanout_tattn_bwd_kernel(
   const float *arow = alpha + (t * k) * heads + L.h;  // read for valid slots of live targets only
   // pass 1: S = Σ_m alpha_m dalpha_m, children in slot order
   double S = 0.0;
-  for (int c0 = 0; c0 < k; c0 += kTatBatch) {
-    float al[kTatBatch];
-    float4 v[kTatBatch];
+  for (int c0 = 0; c0 < k; c0 += kHeadBatch) {
+    float al[kHeadBatch];
+    float4 v[kHeadBatch];
 #pragma unroll
-    for (int u = 0; u < kTatBatch; ++u) {
+    for (int u = 0; u < kHeadBatch; ++u) {
       const bool ok = live && c0 + u < k && (valid == nullptr || valid[t * k + c0 + u] >= 0);
       al[u] = ok ? arow[(int64_t)(c0 + u) * heads] : 0.f;
       v[u] = (act && ok) ? ld4(val + (t * k + c0 + u) * ld_kv + 4 * L.sub) : f4_zero();
     }
 #pragma unroll
-    for (int u = 0; u < kTatBatch; ++u)
-      S = fma((double)al[u], (double)tat_head_sum<POW2>(tat_dot(gg, v[u]), g, L.hb), S);
+    for (int u = 0; u < kHeadBatch; ++u)
+      S = fma((double)al[u], (double)head_sum<POW2>(f4_dot_fma(gg, v[u]), g, L.hb), S);
   }
   // pass 2: ds_j, ∂v_j, ∂k_j and this lane's columns of ∂q
   float4 gqa = f4_zero();
-  for (int c0 = 0; c0 < k; c0 += kTatBatch) {
-    float al[kTatBatch];
-    float4 v[kTatBatch], kr[kTatBatch];
-    bool ok[kTatBatch];
+  for (int c0 = 0; c0 < k; c0 += kHeadBatch) {
+    float al[kHeadBatch];
+    float4 v[kHeadBatch], kr[kHeadBatch];
+    bool ok[kHeadBatch];
 #pragma unroll
-    for (int u = 0; u < kTatBatch; ++u) {
+    for (int u = 0; u < kHeadBatch; ++u) {
       ok[u] = live && c0 + u < k && (valid == nullptr || valid[t * k + c0 + u] >= 0);
       al[u] = ok[u] ? arow[(int64_t)(c0 + u) * heads] : 0.f;
       const int64_t off = (t * k + c0 + u) * ld_kv + 4 * L.sub;
@@ -229,8 +148,8 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void fanout_tattn_bwd_kernel(
       kr[u] = (act && ok[u]) ? ld4(key + off) : f4_zero();
     }
 #pragma unroll
-    for (int u = 0; u < kTatBatch; ++u) {
-      const float da = tat_head_sum<POW2>(tat_dot(gg, v[u]), g, L.hb);
+    for (int u = 0; u < kHeadBatch; ++u) {
+      const float da = head_sum<POW2>(f4_dot_fma(gg, v[u]), g, L.hb);
       const float ds = ok[u] ? (float)((double)al[u] * ((double)da - S) * (double)scale) : 0.f;
       gqa = f4_fma(ds, kr[u], gqa);
       if (act && c0 + u < k) {
@@ -259,43 +178,34 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void csr_tattn_kernel(
     const float *__restrict__ q, const float *__restrict__ skip, int64_t ld_q,
     const float *__restrict__ key, const float *__restrict__ val, int64_t ld_kv, int64_t n_rows,
     int32_t d4, int32_t g, int32_t lg, float scale, float *__restrict__ out) {
-  const TatLane L = tat_lane(lg, d4, g);
+  const HeadLane L = head_lane(lg, d4, g);
   const int64_t r = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> lg;
   const bool live = r < n_rows;
   const bool act = live && L.col;
   const int64_t D = (int64_t)d4 * 4;
   const float4 qv = act ? ld4(q + r * ld_q + 4 * L.sub) : f4_zero();
   const int64_t beg = live ? rowptr[r] : 0, end = live ? rowptr[r + 1] : 0;
-  TatState S = tat_init();
-  for (int64_t j0 = beg; j0 < end; j0 += kTatBatch) {
-    bool ok[kTatBatch];
-    float4 kr[kTatBatch], vr[kTatBatch];
+  SoftmaxState S = softmax_empty();
+  for (int64_t j0 = beg; j0 < end; j0 += kHeadBatch) {
+    bool ok[kHeadBatch];
+    float4 kr[kHeadBatch], vr[kHeadBatch];
 #pragma unroll
-    for (int u = 0; u < kTatBatch; ++u) {
+    for (int u = 0; u < kHeadBatch; ++u) {
       const int32_t src = j0 + u < end ? col[j0 + u] : -1;
       ok[u] = src >= 0 && src < n_rows;
       const int64_t off = (int64_t)src * ld_kv + 4 * L.sub;
       kr[u] = (L.col && ok[u]) ? ld4(key + off) : f4_zero();
       vr[u] = (L.col && ok[u]) ? ld4(val + off) : f4_zero();
     }
-    float s[kTatBatch];
+    float s[kHeadBatch];
 #pragma unroll
-    for (int u = 0; u < kTatBatch; ++u)
-      s[u] = tat_head_sum<POW2>(tat_dot(qv, kr[u]), g, L.hb) * scale;
-    tat_fold(S, s, vr, ok);
+    for (int u = 0; u < kHeadBatch; ++u)
+      s[u] = head_sum<POW2>(f4_dot_fma(qv, kr[u]), g, L.hb) * scale;
+    softmax_fold(S, s, vr, ok);
   }
   if (act)
     tat_store(S, skip != nullptr ? skip + r * ld_q + 4 * L.sub : nullptr, out + r * D + 4 * L.sub);
 }
-
-static bool tat_shape_ok(int32_t k, int32_t heads, int32_t ch) {
-  return heads >= 1 && heads <= 8 && ch >= 4 && ch % 4 == 0 && heads * ch <= 256 && k >= 1 &&
-         k <= 64;
-}
-
-static bool tat_stride_ok(int64_t ld, int32_t D) { return ld >= D && ld % 4 == 0; }
-
-static bool tat_aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace mirec
 
@@ -305,26 +215,18 @@ extern "C" int mirec_fanout_tattn(const float *query, const float *skip, int64_t
                                   int32_t heads, int32_t ch, float scale, float *out,
                                   float *alpha, mirec_stream_t stream) {
   using namespace mirec;
-  MIREC_CHECK_ARG(n_targets >= 0 && tat_shape_ok(k, heads, ch) && scale == scale);
+  MIREC_CHECK_ARG(n_targets >= 0 && head_shape_ok(k, heads, ch) && scale == scale);
   const int D = heads * ch;
-  MIREC_CHECK_ARG(tat_stride_ok(ld_q, D) && tat_stride_ok(ld_kv, D));
+  MIREC_CHECK_ARG(head_stride_ok(ld_q, D) && head_stride_ok(ld_kv, D));
   if (n_targets == 0) return MIREC_OK;
   MIREC_CHECK_ARG(query && key && value && out);
-  MIREC_CHECK_ARG(tat_aligned16(query) && tat_aligned16(skip) && tat_aligned16(key) &&
-                  tat_aligned16(value) && tat_aligned16(out) && tat_aligned16(alpha));
+  MIREC_CHECK_ARG(aligned16(query) && aligned16(skip) && aligned16(key) && aligned16(value) &&
+                  aligned16(out) && aligned16(alpha));
   const int d4 = D / 4, g = ch / 4, lg = row_lg(d4);
-  const int64_t blocks = (n_targets + (256 >> lg) - 1) / (256 >> lg);
-  MIREC_CHECK_ARG(blocks < ((int64_t)1 << 31));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if ((g & (g - 1)) == 0)
-    hipLaunchKernelGGL(fanout_tattn_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, query,
-                       skip, ld_q, key, value, ld_kv, valid, n_targets, k, heads, d4, g, lg,
-                       scale, out, alpha);
-  else
-    hipLaunchKernelGGL(fanout_tattn_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st,
-                       query, skip, ld_q, key, value, ld_kv, valid, n_targets, k, heads, d4, g,
-                       lg, scale, out, alpha);
-  MIREC_LAUNCH_CHECK();
+  MIREC_HEADROW_LAUNCH(fanout_tattn_kernel, head_blocks(n_targets, lg), g, st, query, skip, ld_q,
+                       key, value, ld_kv, valid, n_targets, k, heads, d4, g, lg, scale, out,
+                       alpha);
   return MIREC_OK;
 }
 
@@ -336,32 +238,21 @@ extern "C" int mirec_fanout_tattn_bwd(const float *grad_out, const float *query,
                                       int64_t ld_gq, float *grad_key, float *grad_value,
                                       int64_t ld_gkv, mirec_stream_t stream) {
   using namespace mirec;
-  MIREC_CHECK_ARG(n_targets >= 0 && tat_shape_ok(k, heads, ch) && scale == scale);
+  MIREC_CHECK_ARG(n_targets >= 0 && head_shape_ok(k, heads, ch) && scale == scale);
   const int D = heads * ch;
-  MIREC_CHECK_ARG(tat_stride_ok(ld_q, D) && tat_stride_ok(ld_kv, D) && tat_stride_ok(ld_gq, D) &&
-                  tat_stride_ok(ld_gkv, D));
+  MIREC_CHECK_ARG(head_stride_ok(ld_q, D) && head_stride_ok(ld_kv, D) &&
+                  head_stride_ok(ld_gq, D) && head_stride_ok(ld_gkv, D));
   if (n_targets == 0) return MIREC_OK;
   MIREC_CHECK_ARG(grad_out && query && key && value && alpha && grad_query && grad_key &&
                   grad_value);
-  MIREC_CHECK_ARG(tat_aligned16(grad_out) && tat_aligned16(query) && tat_aligned16(key) &&
-                  tat_aligned16(value) && tat_aligned16(alpha) && tat_aligned16(grad_query) &&
-                  tat_aligned16(grad_skip) && tat_aligned16(grad_key) &&
-                  tat_aligned16(grad_value));
+  MIREC_CHECK_ARG(aligned16(grad_out) && aligned16(query) && aligned16(key) &&
+                  aligned16(value) && aligned16(alpha) && aligned16(grad_query) &&
+                  aligned16(grad_skip) && aligned16(grad_key) && aligned16(grad_value));
   const int d4 = D / 4, g = ch / 4, lg = row_lg(d4);
-  const int64_t blocks = (n_targets + (256 >> lg) - 1) / (256 >> lg);
-  MIREC_CHECK_ARG(blocks < ((int64_t)1 << 31));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if ((g & (g - 1)) == 0)
-    hipLaunchKernelGGL(fanout_tattn_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st,
-                       grad_out, query, ld_q, key, value, ld_kv, valid, alpha, n_targets, k, heads,
-                       d4, g, lg, scale, grad_query, grad_skip, ld_gq, grad_key, grad_value,
-                       ld_gkv);
-  else
-    hipLaunchKernelGGL(fanout_tattn_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st,
-                       grad_out, query, ld_q, key, value, ld_kv, valid, alpha, n_targets, k, heads,
-                       d4, g, lg, scale, grad_query, grad_skip, ld_gq, grad_key, grad_value,
-                       ld_gkv);
-  MIREC_LAUNCH_CHECK();
+  MIREC_HEADROW_LAUNCH(fanout_tattn_bwd_kernel, head_blocks(n_targets, lg), g, st, grad_out,
+                       query, ld_q, key, value, ld_kv, valid, alpha, n_targets, k, heads, d4, g,
+                       lg, scale, grad_query, grad_skip, ld_gq, grad_key, grad_value, ld_gkv);
   return MIREC_OK;
 }
 
@@ -370,25 +261,17 @@ extern "C" int mirec_csr_tattn(const mirec_csr_t *csr, const float *query, const
                                int32_t heads, int32_t ch, float scale, float *out,
                                mirec_stream_t stream) {
   using namespace mirec;
-  MIREC_CHECK_ARG(csr && csr->n_rows >= 0 && tat_shape_ok(1, heads, ch) && scale == scale);
+  MIREC_CHECK_ARG(csr && csr->n_rows >= 0 && head_shape_ok(1, heads, ch) && scale == scale);
   const int D = heads * ch;
-  MIREC_CHECK_ARG(tat_stride_ok(ld_q, D) && tat_stride_ok(ld_kv, D));
+  MIREC_CHECK_ARG(head_stride_ok(ld_q, D) && head_stride_ok(ld_kv, D));
   if (csr->n_rows == 0) return MIREC_OK;
   MIREC_CHECK_ARG(csr->rowptr && csr->col && query && key && value && out);
-  MIREC_CHECK_ARG(tat_aligned16(query) && tat_aligned16(skip) && tat_aligned16(key) &&
-                  tat_aligned16(value) && tat_aligned16(out));
+  MIREC_CHECK_ARG(aligned16(query) && aligned16(skip) && aligned16(key) && aligned16(value) &&
+                  aligned16(out));
   const int d4 = D / 4, g = ch / 4, lg = row_lg(d4);
-  const int64_t blocks = (csr->n_rows + (256 >> lg) - 1) / (256 >> lg);
-  MIREC_CHECK_ARG(blocks < ((int64_t)1 << 31));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if ((g & (g - 1)) == 0)
-    hipLaunchKernelGGL(csr_tattn_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st,
-                       csr->rowptr, csr->col, query, skip, ld_q, key, value, ld_kv, csr->n_rows,
-                       d4, g, lg, scale, out);
-  else
-    hipLaunchKernelGGL(csr_tattn_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st,
-                       csr->rowptr, csr->col, query, skip, ld_q, key, value, ld_kv, csr->n_rows,
-                       d4, g, lg, scale, out);
-  MIREC_LAUNCH_CHECK();
+  MIREC_HEADROW_LAUNCH(csr_tattn_kernel, head_blocks(csr->n_rows, lg), g, st, csr->rowptr,
+                       csr->col, query, skip, ld_q, key, value, ld_kv, csr->n_rows, d4, g, lg,
+                       scale, out);
   return MIREC_OK;
 }

@@ -17,17 +17,8 @@ import torch.nn as nn
 from . import _lib
 from ._lib import check, lib
 from .graph import Graph
+from .headrow import check_shape
 from .linear import col_sums, linear
-
-MAX_HEADS, MAX_WIDTH, MAX_FANOUT = 8, 256, 64
-
-
-def _check_shape(k: int, heads: int, ch: int):
-    if not (1 <= heads <= MAX_HEADS and ch >= 4 and ch % 4 == 0 and heads * ch <= MAX_WIDTH
-            and 1 <= k <= MAX_FANOUT):
-        raise ValueError("GAT hop: heads <= 8, channels per head a multiple of 4, heads * "
-                         f"channels <= 256 and 1 <= fanout <= 64 (got k={k}, heads={heads}, "
-                         f"channels={ch})")
 
 
 class _FanoutGAT(torch.autograd.Function):
@@ -88,7 +79,7 @@ def fanout_gat(z_child: torch.Tensor, z_self: torch.Tensor, valid: torch.Tensor 
     D = z_self.shape[1]
     if D % heads:
         raise ValueError("fanout_gat: the row width must be heads * channels")
-    _check_shape(int(k), int(heads), D // heads)
+    check_shape("GAT hop", int(k), int(heads), D // heads)
     if not (z_self.is_cuda and z_self.dtype == torch.float32 and z_child.dtype == torch.float32):
         raise ValueError("fanout_gat: float32 rows on a HIP device")
     if att_src.numel() != D or att_dst.numel() != D or (bias is not None and bias.numel() != D):
@@ -109,7 +100,7 @@ def csr_gat(graph: Graph, z: torch.Tensor, att_src: torch.Tensor, att_dst: torch
     n, D = z.shape
     if n != graph.n_nodes or D % heads:
         raise ValueError("csr_gat: z holds one row of heads * channels floats per node")
-    _check_shape(1, int(heads), D // heads)
+    check_shape("GAT hop", 1, int(heads), D // heads)
     z = z.contiguous()
     out = torch.empty_like(z)
     logits = torch.empty(n, 2 * heads, dtype=z.dtype, device=z.device)
@@ -137,7 +128,7 @@ class GATHop(nn.Module):
 
     def __init__(self, d_in: int, heads: int, ch: int, slope: float = 0.2, device=None):
         super().__init__()
-        _check_shape(1, heads, ch)
+        check_shape("GAT hop", 1, heads, ch)
         self.d_in, self.heads, self.ch, self.slope = int(d_in), int(heads), int(ch), float(slope)
         self.lin = _Projection(d_in, heads * ch, device=device)
         self.att_src = nn.Parameter(torch.empty(1, heads, ch, device=device))

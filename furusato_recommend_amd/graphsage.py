@@ -40,6 +40,7 @@ from . import engine as _engine
 from ._lib import CSR, IN_PRESCALED, Prop, check, lib
 from .engine import AdamGroup, AdamState, sample_triples
 from .graph import DEFAULT_SPLIT, Graph, positive_probs
+from .headrow import check_shape
 from .linear import Linear, sage_linear
 from .rows import slice_norms2
 
@@ -482,9 +483,26 @@ class _ChunkTrees:
         return (self[k] for k in range(len(self)))
 
 
-class GraphSAGE(nn.Module):
+class TreeModel(nn.Module):
+    """What the sampled-tree models (GraphSAGE, gnn.GNN, tgrec.TGRec) share:
+    the configuration, the [N, d] id table and its sorted gradient, the
+    graph and its samplers, the trainer surface and, for a model that says
+    no more, the plain step (the table's gradient materialised, Adam over
+    every parameter), the full-graph inference through ``convs[i].full`` and
+    the loss whose norm term covers the two table slices only.
+
+    A subclass registers its layers in ``build_layers`` — called between the
+    registration of the (empty) table and ``init_parameters``, so the table
+    is the first parameter and the layers draw their initial values before
+    it does — and defines ``forward(tree, dropout_seed)``."""
+
+    HOP = None         # hop layer HOP(d, heads, d // heads, device=...) of ``convs``
+    HEADS = None       # default head count
+    HEAVY_SLICE = 0    # the table slice (0 users, 1 items) with weight 2 in the norm term
+
     def __init__(self, config: dict, dataset):
         super().__init__()
+        name = type(self).__name__
         self.config = config
         self.n_user = self.num_users = int(dataset.n_users)
         self.m_item = self.num_items = int(dataset.m_items)
@@ -495,6 +513,8 @@ class GraphSAGE(nn.Module):
         if len(self.sizes) != L:
             raise ValueError("fanouts must have one size per layer")
         self.dropout_p = float(config.get("dropout_p", 0.2))
+        if not 0.0 <= self.dropout_p < 1.0:
+            raise ValueError("dropout_p must lie in [0, 1)")
         # neighbour sampling: without replacement (False, default: PyG's
         # NeighborSampler of graphsage.py:342-365 — all neighbours when the
         # degree is <= the fanout) or with replacement (True: the repo's
@@ -502,42 +522,37 @@ class GraphSAGE(nn.Module):
         self.fanout_replace = bool(config.get("fanout_replace", False))
         self.device = torch.device(config.get("device", "cuda:0"))
         if self.device.type != "cuda":
-            raise RuntimeError("GraphSAGE (furusato_recommend_amd) runs on a HIP device only")
-        if d % 4 != 0:
-            raise ValueError("recdim must be a multiple of 4")
+            raise RuntimeError(f"{name} (furusato_recommend_amd) runs on a HIP device only")
         n = self.n_user + self.m_item
         # one [N, d] table; the reference's two id tables are views into it
         self._table = nn.Parameter(torch.empty(n, d, device=self.device))
-        self.w_linears = nn.ModuleList(
-            [Linear(2 * d, d, device=self.device) for _ in range(L)])
+        self.build_layers()
         self.init_parameters()
         self.graph = Graph.from_interactions(dataset.trainUser, dataset.trainItem,
                                              self.n_user, self.m_item, self.device,
                                              split=int(config.get("csr_split", DEFAULT_SPLIT)))
         self.graph.set_positive_probs(positive_probs(config))
-        deg = torch.from_numpy(self.graph.degree()).to(self.device).float()
-        self._mean_dinv = torch.where(deg > 0, 1.0 / deg.clamp(min=1), torch.zeros_like(deg))
-        # the table's Adam state is stepped by the fused kernel (TableGrad.adam)
-        # or, when its gradient is materialised, with the others
-        self._table_state = AdamState(self._table, lr=config["lr"])
-        self.optims = AdamGroup([self._table_state] +
-                                [AdamState(p, lr=config["lr"]) for p in self.w_linears.parameters()])
+        self.optims = AdamGroup([AdamState(p, lr=config["lr"]) for p in self.parameters()])
         self._tg = TableGrad(n, self.n_user, d, self.device)
-        self._norm_cache = None  # (norms [2], token) of the table after the fused Adam
+        self._tg.dense = True  # the gradient is materialised as the table's .grad
         self._step_seed = int(config.get("seed", 2020))
         self._calls = 0
-        # set by DenseGradDataParallel's ``fetch`` exchange: the local table
-        # is current on this rank's row block and the fetched rows only
-        # until sync_table() / gather_optimizer_state() (collectives) run
-        self.table_stale = False
-        self.register_state_dict_pre_hook(
-            lambda module, prefix, keep_vars: module._check_table_current("state_dict()"))
+        self._slice_norms2 = None
 
-    def _check_table_current(self, what: str):
-        if self.table_stale:
-            raise RuntimeError(f"GraphSAGE.{what}: the id table is current on this rank's row "
-                               "block only (data-parallel 'fetch' exchange); call "
-                               "sync_table() or gather_optimizer_state() on every rank first")
+    def build_layers(self):
+        """``convs``: one HOP per layer, ``heads`` heads of d / heads channels."""
+        name, d = type(self).__name__, self.latent_dim
+        self.heads = H = int(self.config.get("heads", self.HEADS))
+        if H < 1 or d % (4 * H) != 0:
+            raise ValueError(f"{name}: recdim must be a multiple of 4 * heads")
+        for k in self.sizes:
+            check_shape(name, k, H, d // H)
+        self.convs = nn.ModuleList([self.HOP(d, H, d // H, device=self.device)
+                                    for _ in range(self.num_layers)])
+
+    def init_parameters(self):
+        with torch.no_grad():
+            nn.init.normal_(self._table, std=0.1)  # graphsage.py:123-133, gain 0.1
 
     @property
     def user_id_embeddings(self):
@@ -546,15 +561,6 @@ class GraphSAGE(nn.Module):
     @property
     def item_id_embeddings(self):
         return self._table[self.n_user:]
-
-    def init_parameters(self):
-        # graphsage.py:123-133 (gain 0.1; the last w_linear at gain 1)
-        gain = 0.1
-        with torch.no_grad():
-            nn.init.normal_(self._table, std=gain)
-            for i, w in enumerate(self.w_linears):
-                nn.init.xavier_uniform_(w.weight, gain=1.0 if i == self.num_layers - 1 else gain)
-                nn.init.zeros_(w.bias)
 
     # ------------------------------------------------------------ sampling
     def sample_tree(self, seeds: torch.Tensor, seed: int) -> SampleTree:
@@ -581,6 +587,162 @@ class GraphSAGE(nn.Module):
 
         expand(root)
         return tree
+
+    def _seed_nodes(self, users, pos, neg):
+        """The 3B seeds (users, pos + n_user, neg + n_user) of a batch."""
+        u32, p32, n32 = (torch.as_tensor(t).to(device=self.device, dtype=torch.int32)
+                         .contiguous() for t in (users, pos, neg))
+        seeds = torch.empty(3 * u32.numel(), dtype=torch.int32, device=u32.device)
+        check(lib.mirec_pack_seed_nodes(u32.data_ptr(), p32.data_ptr(), n32.data_ptr(),
+                                        u32.numel(), self.n_user, seeds.data_ptr(),
+                                        _lib.stream_handle()), "pack_seed_nodes")
+        return seeds
+
+    def sample(self, n_triples: int, seed: int, offset: int = 0, shard: int = 0,
+               n_shards: int = 1):
+        u = torch.empty(n_triples, dtype=torch.int32, device=self.device)
+        p, n = torch.empty_like(u), torch.empty_like(u)
+        err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        sample_triples(self.graph, n_triples, seed, offset, u, p, n, err, shard, n_shards)
+        self._sample_err = err
+        return u, p, n
+
+    def _dropout(self, x: torch.Tensor, p: float, seed: int) -> torch.Tensor:
+        """x under the mask of ``seed``, the kept values scaled by 1 / (1 - p)."""
+        if p == 0.0:
+            return x
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(seed & ((1 << 62) - 1))
+        keep = torch.rand(x.shape, generator=gen, device=x.device) >= p
+        return x * keep.to(x.dtype).mul_(1.0 / (1.0 - p))
+
+    # ---------------------------------------------------------------- loss
+    def loss(self, user_emb, pos_emb, neg_emb):
+        """mean softplus(neg - pos) + decay * (2 |heavy| + |light|) / B, the
+        two table slices' norms in the model's order (HEAVY_SLICE)."""
+        pos_scores = torch.sum(user_emb * pos_emb, dim=1)
+        neg_scores = torch.sum(user_emb * neg_emb, dim=1)
+        n2 = self._slice_norms2
+        self._slice_norms2 = None
+        if n2 is None:
+            n2 = (self._table[: self.n_user].norm(2), self._table[self.n_user:].norm(2))
+        heavy, light = n2[self.HEAVY_SLICE], n2[1 - self.HEAVY_SLICE]
+        all_param = (heavy + heavy + light) / user_emb.size(0)
+        return torch.mean(F.softplus(neg_scores - pos_scores)) + all_param * self.config["decay"]
+
+    def loss_fused(self, emb: torch.Tensor) -> torch.Tensor:
+        """loss() on the forward's seed embeddings [u ; p ; n] in two launches
+        (_SageLoss with no small parameters weighs its two norms 2 and 1: it
+        is fed the slice norms heavy first)."""
+        n2 = self._slice_norms2
+        if n2 is None or not emb.is_contiguous() or emb.shape[1] % 4:
+            B = emb.shape[0] // 3
+            return self.loss(emb[:B], emb[B:2 * B], emb[2 * B:])
+        self._slice_norms2 = None
+        return _SageLoss.apply(emb, n2 if self.HEAVY_SLICE == 0 else n2.flip(0),
+                               float(self.config["decay"]))
+
+    # ------------------------------------------------------------ training
+    @torch.no_grad()
+    def optimizer_step(self):
+        self.optims.step()
+        self._tg.pending = False
+
+    def stageOne(self, users, pos, neg, tree: SampleTree | None = None):
+        """One BPR step: sample the tree over [users ; pos ; neg] (or take
+        ``tree``), forward, loss, backward, Adam over every parameter."""
+        seed = self._step_seed * 7919 + self._calls
+        self._calls += 1
+        for p in self.parameters():
+            p.grad = None
+        if tree is None:
+            tree = self.sample_tree(self._seed_nodes(users, pos, neg), seed)
+        emb = self.forward(tree, dropout_seed=seed if self.training else None)
+        loss = self.loss_fused(emb)
+        with _BWD_ON_CALLER():
+            loss.backward()
+        self.optimizer_step()
+        return loss.detach()
+
+    def OneEpoch(self, user, pos, neg):
+        B = int(self.config["bpr_batch_size"])
+        n = len(user)
+        user, pos, neg = (torch.as_tensor(t).to(self.device) for t in (user, pos, neg))
+        acc = torch.zeros((), device=self.device)
+        for i in range(0, n, B):
+            acc += self.stageOne(user[i:i + B], pos[i:i + B], neg[i:i + B])
+        return acc / (n // B + 1)
+
+    # ----------------------------------------------------------- inference
+    @torch.no_grad()
+    def propagated(self) -> torch.Tensor:
+        """Full-graph inference: per layer the hop over ALL neighbours of
+        every node (``convs[i].full``), ReLU except after the last layer; no
+        dropout."""
+        x = self._table.detach()
+        for i, conv in enumerate(self.convs):
+            x = conv.full(self.graph, x)
+            if i != self.num_layers - 1:
+                x = x.relu_()
+        return x
+
+    @torch.no_grad()
+    def eval_embeddings(self):
+        """(user rows, item rows) of one full-graph propagation: the operands
+        of the streamed evaluation (evaluate.score_topk / evaluate_ranked)."""
+        out = self.propagated()
+        return out[: self.n_user], out[self.n_user:]
+
+    @torch.no_grad()
+    def eval_ratings(self):
+        out = self.propagated()
+        items = out[self.n_user:]
+        return lambda users: out[users.long()] @ items.t()
+
+    @torch.no_grad()
+    def getUsersRating(self, users):
+        return self.eval_ratings()(torch.as_tensor(users, device=self.device))
+
+
+class GraphSAGE(TreeModel):
+    def __init__(self, config: dict, dataset):
+        super().__init__(config, dataset)
+        deg = torch.from_numpy(self.graph.degree()).to(self.device).float()
+        self._mean_dinv = torch.where(deg > 0, 1.0 / deg.clamp(min=1), torch.zeros_like(deg))
+        # the table's Adam state is stepped by the fused kernel (TableGrad.adam,
+        # which forms the gradient itself) or, when the gradient is
+        # materialised (data parallelism sets ``_tg.dense``), with the others
+        self._table_state = self.optims.states[0]
+        self._tg.dense = False
+        self._norm_cache = None  # (norms [2], token) of the table after the fused Adam
+        # set by DenseGradDataParallel's ``fetch`` exchange: the local table
+        # is current on this rank's row block and the fetched rows only
+        # until sync_table() / gather_optimizer_state() (collectives) run
+        self.table_stale = False
+        self.register_state_dict_pre_hook(
+            lambda module, prefix, keep_vars: module._check_table_current("state_dict()"))
+
+    def build_layers(self):
+        d = self.latent_dim
+        if d % 4 != 0:
+            raise ValueError("recdim must be a multiple of 4")
+        self.w_linears = nn.ModuleList(
+            [Linear(2 * d, d, device=self.device) for _ in range(self.num_layers)])
+
+    def init_parameters(self):
+        # graphsage.py:123-133 (gain 0.1; the last w_linear at gain 1)
+        gain = 0.1
+        with torch.no_grad():
+            nn.init.normal_(self._table, std=gain)
+            for i, w in enumerate(self.w_linears):
+                nn.init.xavier_uniform_(w.weight, gain=1.0 if i == self.num_layers - 1 else gain)
+                nn.init.zeros_(w.bias)
+
+    def _check_table_current(self, what: str):
+        if self.table_stale:
+            raise RuntimeError(f"GraphSAGE.{what}: the id table is current on this rank's row "
+                               "block only (data-parallel 'fetch' exchange); call "
+                               "sync_table() or gather_optimizer_state() on every rank first")
 
     # ------------------------------------------------------------- forward
     def forward(self, tree: SampleTree, dropout_seed: int | None = None) -> torch.Tensor:
@@ -737,13 +899,7 @@ class GraphSAGE(nn.Module):
             return self._stage_chunks(users, pos, neg, seed, grad_hook, loss_scale, tree_hook,
                                       int(chunks), chunk_hook)
         if tree is None:
-            u32, p32, n32 = (torch.as_tensor(t).to(device=self.device, dtype=torch.int32)
-                             .contiguous() for t in (users, pos, neg))
-            seeds = torch.empty(3 * u32.numel(), dtype=torch.int32, device=u32.device)
-            check(lib.mirec_pack_seed_nodes(u32.data_ptr(), p32.data_ptr(), n32.data_ptr(),
-                                            u32.numel(), self.n_user, seeds.data_ptr(),
-                                            _lib.stream_handle()), "pack_seed_nodes")
-            tree = self.sample_tree(seeds, seed)
+            tree = self.sample_tree(self._seed_nodes(users, pos, neg), seed)
         if tree_hook is not None:
             tree_hook(tree)
         emb = self.forward(tree, dropout_seed=seed if self.training else None)
@@ -766,15 +922,6 @@ class GraphSAGE(nn.Module):
     def chunk_seed(seed: int, k: int) -> int:
         """Tree / dropout seed of micro-batch k of the step with seed ``seed``."""
         return seed * 1009 + k + 1
-
-    def _seed_nodes(self, users, pos, neg):
-        u32, p32, n32 = (torch.as_tensor(t).to(device=self.device, dtype=torch.int32)
-                         .contiguous() for t in (users, pos, neg))
-        seeds = torch.empty(3 * u32.numel(), dtype=torch.int32, device=u32.device)
-        check(lib.mirec_pack_seed_nodes(u32.data_ptr(), p32.data_ptr(), n32.data_ptr(),
-                                        u32.numel(), self.n_user, seeds.data_ptr(),
-                                        _lib.stream_handle()), "pack_seed_nodes")
-        return seeds
 
     def _stage_chunks(self, users, pos, neg, seed, grad_hook, loss_scale, tree_hook, C,
                       chunk_hook):
@@ -824,24 +971,6 @@ class GraphSAGE(nn.Module):
         self.optimizer_step()
         return total
 
-    def OneEpoch(self, user, pos, neg):
-        B = int(self.config["bpr_batch_size"])
-        n = len(user)
-        user, pos, neg = (torch.as_tensor(t).to(self.device) for t in (user, pos, neg))
-        acc = torch.zeros((), device=self.device)
-        for i in range(0, n, B):
-            acc += self.stageOne(user[i:i + B], pos[i:i + B], neg[i:i + B])
-        return acc / (n // B + 1)
-
-    def sample(self, n_triples: int, seed: int, offset: int = 0, shard: int = 0,
-               n_shards: int = 1):
-        u = torch.empty(n_triples, dtype=torch.int32, device=self.device)
-        p, n = torch.empty_like(u), torch.empty_like(u)
-        err = torch.zeros(1, dtype=torch.int32, device=self.device)
-        sample_triples(self.graph, n_triples, seed, offset, u, p, n, err, shard, n_shards)
-        self._sample_err = err
-        return u, p, n
-
     # ----------------------------------------------------------- inference
     @torch.no_grad()
     def propagated(self) -> torch.Tensor:
@@ -856,13 +985,3 @@ class GraphSAGE(nn.Module):
             if i != self.num_layers - 1:
                 x = x.relu()
         return x
-
-    @torch.no_grad()
-    def eval_ratings(self):
-        out = self.propagated()
-        items = out[self.n_user:]
-        return lambda users: out[users.long()] @ items.t()
-
-    @torch.no_grad()
-    def getUsersRating(self, users):
-        return self.eval_ratings()(torch.as_tensor(users, device=self.device))

@@ -26,17 +26,8 @@ import torch.nn as nn
 from . import _lib
 from ._lib import check, lib
 from .graph import Graph
+from .headrow import check_shape
 from .linear import Linear, linear
-
-MAX_HEADS, MAX_WIDTH, MAX_FANOUT = 8, 256, 64
-
-
-def _check_shape(k: int, heads: int, ch: int):
-    if not (1 <= heads <= MAX_HEADS and ch >= 4 and ch % 4 == 0 and heads * ch <= MAX_WIDTH
-            and 1 <= k <= MAX_FANOUT):
-        raise ValueError("transformer hop: heads <= 8, channels per head a multiple of 4, heads "
-                         f"* channels <= 256 and 1 <= fanout <= 64 (got k={k}, heads={heads}, "
-                         f"channels={ch})")
 
 
 def _check_rows(name: str, kv: torch.Tensor, qs: torch.Tensor, heads: int) -> int:
@@ -100,7 +91,7 @@ def fanout_tattn(kv: torch.Tensor, qs: torch.Tensor, valid: torch.Tensor | None,
     D = _check_rows("fanout_tattn", kv, qs, int(heads))
     if kv.shape[0] != qs.shape[0] * k:
         raise ValueError("fanout_tattn: kv holds k child rows per row of qs")
-    _check_shape(int(k), int(heads), D // heads)
+    check_shape("transformer hop", int(k), int(heads), D // heads)
     if valid is not None:
         if valid.numel() != kv.shape[0]:
             raise ValueError("fanout_tattn: one valid flag per child row")
@@ -119,7 +110,7 @@ def csr_tattn(graph: Graph, kv: torch.Tensor, qs: torch.Tensor, heads: int) -> t
     if kv.shape[0] != graph.n_nodes or qs.shape[0] != graph.n_nodes:
         raise ValueError("csr_tattn: kv and qs hold one row per node")
     ch = D // heads
-    _check_shape(1, int(heads), ch)
+    check_shape("transformer hop", 1, int(heads), ch)
     kv, qs = kv.contiguous(), qs.contiguous()
     out = torch.empty(qs.shape[0], D, dtype=qs.dtype, device=qs.device)
     check(lib.mirec_csr_tattn(graph.csr_ptr(), qs.data_ptr(), qs.data_ptr() + 4 * D, 2 * D,
@@ -135,7 +126,7 @@ class TransformerHop(nn.Module):
 
     def __init__(self, d_in: int, heads: int, ch: int, device=None):
         super().__init__()
-        _check_shape(1, heads, ch)
+        check_shape("transformer hop", 1, heads, ch)
         self.d_in, self.heads, self.ch = int(d_in), int(heads), int(ch)
         for name in ("lin_key", "lin_query", "lin_value", "lin_skip"):
             setattr(self, name, Linear(d_in, heads * ch, device=device))

@@ -1,6 +1,6 @@
 """The reference's 'tgrec' model (model/tgrec.py) on the HIP engine:
-GraphSAGE's trainer surface and sampler, the hop a dot-product attention
-layer — TransformerConv(d, d // heads, heads=heads, root_weight=True),
+the trainer surface and sampler of the sampled-tree base class
+(graphsage.TreeModel), the hop a dot-product attention layer — TransformerConv(d, d // heads, heads=heads, root_weight=True),
 tgrec.py:161-171 (heads = 8 there).
 
 In scope: the sampled-tree forward (tgrec.py:280-292: per layer the conv, ReLU
@@ -33,18 +33,16 @@ opposite order to 'gnn' — and the attention parameters carry no norm term.
 The table's rows come from one gather and its gradient from the sorted row
 sums of graphsage.TableGrad in its dense form (a fixed summation order; the
 attention backward is plain stores, so a step repeats bitwise; Adam then runs
-over every parameter with AdamGroup).
+over every parameter with AdamGroup).  All of that — the sampler, the step,
+the loss, the inference loop over ``TransformerHop.full`` (mirec_csr_tattn:
+every neighbour plus the skip row, tgrec.py:366-382) — is
+graphsage.TreeModel's; this module adds the hop, the gather and the forward.
 """
 from __future__ import annotations
 
 import torch
-import torch.nn as nn
-import torch.nn.functional as F
 
-from .engine import AdamGroup, AdamState
-from .gnn import GNN
-from .graph import DEFAULT_SPLIT, Graph, positive_probs
-from .graphsage import GraphSAGE, SampleTree, TableGrad, _BWD_ON_CALLER, _SageLoss, _TableTerms
+from .graphsage import SampleTree, TreeModel, _TableTerms
 from .tconv import TransformerHop
 
 MAX_TABLE_OUTPUTS = 8  # MIREC_TABLE_GRAD_MAX_GROUPS: row groups of one table gradient
@@ -58,67 +56,10 @@ def _split(x, sizes):
     return [x] if len(sizes) == 1 else list(x.split(sizes))
 
 
-class TGRec(nn.Module):
-    def __init__(self, config: dict, dataset):
-        super().__init__()
-        self.config = config
-        self.n_user = self.num_users = int(dataset.n_users)
-        self.m_item = self.num_items = int(dataset.m_items)
-        self.latent_dim = d = int(config.get("recdim", 128))
-        self.num_layers = L = int(config.get("layer", 2))
-        self.heads = H = int(config.get("heads", 8))  # tgrec.py:162
-        k = int(config.get("num_neighbors", 5))
-        self.sizes = [int(s) for s in config.get("fanouts", [k] * L)]
-        if len(self.sizes) != L:
-            raise ValueError("fanouts must have one size per layer")
-        if H < 1 or d % (4 * H) != 0:
-            raise ValueError("recdim must be a multiple of 4 * heads")
-        if H > 8 or d > 256 or not all(1 <= s <= 64 for s in self.sizes):
-            raise ValueError("TGRec: heads <= 8, recdim <= 256, fanouts in 1..64")
-        self.dropout_p = float(config.get("dropout_p", 0.2))  # tgrec.py: nn.Dropout(0.2)
-        if not 0.0 <= self.dropout_p < 1.0:
-            raise ValueError("dropout_p must lie in [0, 1)")
-        self.fanout_replace = bool(config.get("fanout_replace", False))
-        self.device = torch.device(config.get("device", "cuda:0"))
-        if self.device.type != "cuda":
-            raise RuntimeError("TGRec (furusato_recommend_amd) runs on a HIP device only")
-        n = self.n_user + self.m_item
-        # one [N, d] table; the reference's two id tables are views into it
-        self._table = nn.Parameter(torch.empty(n, d, device=self.device))
-        self.convs = nn.ModuleList([TransformerHop(d, H, d // H, device=self.device)
-                                    for _ in range(L)])
-        with torch.no_grad():
-            nn.init.normal_(self._table, std=0.1)  # GraphSAGE's id-table init
-        self.graph = Graph.from_interactions(dataset.trainUser, dataset.trainItem,
-                                             self.n_user, self.m_item, self.device,
-                                             split=int(config.get("csr_split", DEFAULT_SPLIT)))
-        self.graph.set_positive_probs(positive_probs(config))
-        self.optims = AdamGroup([AdamState(p, lr=config["lr"]) for p in self.parameters()])
-        self._tg = TableGrad(n, self.n_user, d, self.device)
-        self._tg.dense = True  # the gradient is materialised as the table's .grad
-        self._step_seed = int(config.get("seed", 2020))
-        self._calls = 0
-        self._slice_norms2 = None
+class TGRec(TreeModel):
+    HOP, HEADS = TransformerHop, 8  # tgrec.py:162
+    HEAVY_SLICE = 1  # all_param = 2 |I| + |U| (tgrec.py:294-306)
 
-    @property
-    def user_id_embeddings(self):
-        return self._table[: self.n_user]
-
-    @property
-    def item_id_embeddings(self):
-        return self._table[self.n_user:]
-
-    # the sampler and the trainer's helpers are GraphSAGE's own, the seeded
-    # dropout mask is GNN's
-    sample_tree = GraphSAGE.sample_tree
-    sample = GraphSAGE.sample
-    OneEpoch = GraphSAGE.OneEpoch
-    _seed_nodes = GraphSAGE._seed_nodes
-    eval_ratings = GraphSAGE.eval_ratings
-    getUsersRating = GraphSAGE.getUsersRating
-    _dropout = GNN._dropout
-
-    # ------------------------------------------------------------- forward
     def _gather(self, tree: SampleTree):
         """The tree's table rows: (rows per group, rows of the leaf groups as
         they lie, rows of the other groups as they lie).  Consecutive groups
@@ -183,72 +124,3 @@ class TGRec(nn.Module):
                 new[gi] = out
             h = new
         return h[0]
-
-    # ---------------------------------------------------------------- loss
-    def loss(self, user_emb, pos_emb, neg_emb):
-        """tgrec.py:294-306: mean softplus(neg - pos) + decay * (2 |I| + |U|) / B
-        (see the module docstring for the norm term)."""
-        pos_scores = torch.sum(user_emb * pos_emb, dim=1)
-        neg_scores = torch.sum(user_emb * neg_emb, dim=1)
-        n2 = self._slice_norms2
-        self._slice_norms2 = None
-        if n2 is None:
-            nu, ni = self._table[: self.n_user].norm(2), self._table[self.n_user:].norm(2)
-        else:
-            nu, ni = n2[0], n2[1]
-        all_param = (ni + ni + nu) / user_emb.size(0)
-        return torch.mean(F.softplus(neg_scores - pos_scores)) + all_param * self.config["decay"]
-
-    def loss_fused(self, emb: torch.Tensor) -> torch.Tensor:
-        """loss() on the forward's seed embeddings [u ; p ; n] in two launches
-        (graphsage._SageLoss with no small parameters weighs its two norms 2
-        and 1: it is fed (|I|, |U|), the slice norms swapped)."""
-        n2 = self._slice_norms2
-        if n2 is None or not emb.is_contiguous() or emb.shape[1] % 4:
-            B = emb.shape[0] // 3
-            return self.loss(emb[:B], emb[B:2 * B], emb[2 * B:])
-        self._slice_norms2 = None
-        return _SageLoss.apply(emb, n2.flip(0), float(self.config["decay"]))
-
-    # ------------------------------------------------------------ training
-    @torch.no_grad()
-    def optimizer_step(self):
-        self.optims.step()
-        self._tg.pending = False
-
-    def stageOne(self, users, pos, neg, tree: SampleTree | None = None):
-        """One BPR step: sample the tree over [users ; pos ; neg] (or take
-        ``tree``), forward, loss, backward, Adam over every parameter."""
-        seed = self._step_seed * 7919 + self._calls
-        self._calls += 1
-        for p in self.parameters():
-            p.grad = None
-        if tree is None:
-            tree = self.sample_tree(self._seed_nodes(users, pos, neg), seed)
-        emb = self.forward(tree, dropout_seed=seed if self.training else None)
-        loss = self.loss_fused(emb)
-        with _BWD_ON_CALLER():
-            loss.backward()
-        self.optimizer_step()
-        return loss.detach()
-
-    # ----------------------------------------------------------- inference
-    @torch.no_grad()
-    def propagated(self) -> torch.Tensor:
-        """Full-graph inference (tgrec.py:366-382): per layer the four
-        projections (two stacked GEMMs), the attention of every node over ALL
-        its neighbours plus its skip row (mirec_csr_tattn), ReLU except after
-        the last layer; no dropout."""
-        x = self._table.detach()
-        for i, conv in enumerate(self.convs):
-            x = conv.full(self.graph, x)
-            if i != self.num_layers - 1:
-                x = x.relu_()
-        return x
-
-    @torch.no_grad()
-    def eval_embeddings(self):
-        """(user rows, item rows) of one full-graph propagation: the operands
-        of the streamed evaluation (evaluate.score_topk / evaluate_ranked)."""
-        out = self.propagated()
-        return out[: self.n_user], out[self.n_user:]
