@@ -72,6 +72,12 @@ class Drop(Structure):
     _fields_ = [("keep_prob", c_float), ("transposed", c_int32), ("seed", c_uint64)]
 
 
+class SeedBits(Structure):
+    """mirec_seed_bits_t (bit forms of the seed set S, user range first)."""
+    _fields_ = [("bits", c_void_p), ("split", c_int64), ("shift", c_int32 * 2),
+                ("words", c_int32 * 2)]
+
+
 class Sweep(Structure):
     """mirec_sweep_t (column-sweep layout of the item rows)."""
     _fields_ = [
@@ -167,6 +173,11 @@ SIGNATURES = {
     "mirec_frontier": (c_int, [POINTER(CSR), c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_int32, c_void_p]),
+    "mirec_seed_bits_sizeof": (c_size_t, []),
+    "mirec_frontier_bits": (c_int, [POINTER(CSR), c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                    c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int32, POINTER(SeedBits), c_void_p]),
+    "mirec_propagate_seeded": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(SeedBits), c_void_p]),
     "mirec_mask_compact_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "mirec_small_sort_workspace": (c_int, [c_int64, POINTER(c_size_t)]),
@@ -476,6 +487,8 @@ def _load():
         raise ImportError("struct layout mismatch: mirec_sweep_wave_t")
     if lib.mirec_sweep_pace_sizeof() != ctypes.sizeof(SweepPace):
         raise ImportError("struct layout mismatch: mirec_sweep_pace_t")
+    if lib.mirec_seed_bits_sizeof() != ctypes.sizeof(SeedBits):
+        raise ImportError("struct layout mismatch: mirec_seed_bits_t")
     return lib
 
 

@@ -66,6 +66,37 @@ __device__ __forceinline__ float4 ld4(const float *p) {
 __device__ __forceinline__ void st4(float *p, float4 v) {
   *reinterpret_cast<float4 *>(p) = v;
 }
+// mirec_seed_bits_t on the device (frontier.hip sets the bits in memory,
+// prop.hip tests them in LDS): the position of a node's bit counted from bit
+// 0 of word 0, range 1's words following range 0's.
+struct SeedBitsK {
+  uint32_t *bits;
+  int32_t split;
+  int32_t shift0, shift1;
+  int32_t words0, words1;
+};
+__device__ __forceinline__ uint32_t seed_bit_pos(const SeedBitsK &f, int32_t node) {
+  const bool hi = node >= f.split;
+  const uint32_t b = hi ? (uint32_t)(node - f.split) >> f.shift1 : (uint32_t)node >> f.shift0;
+  return (hi ? (uint32_t)f.words0 * 32u : 0u) + b;
+}
+// (host) the arrays cover both ranges of an n_rows-node graph
+inline bool seed_bits_valid(const mirec_seed_bits_t *s, int64_t n_rows) {
+  if (s->bits == nullptr || ((uintptr_t)s->bits & 3u) != 0) return false;
+  if (s->split < 0 || s->split > n_rows || n_rows > INT32_MAX) return false;
+  const int64_t n[2] = {s->split, n_rows - s->split};
+  for (int r = 0; r < 2; ++r) {
+    if (s->shift[r] < 0 || s->shift[r] > 31 || s->words[r] < 0 || s->words[r] > (1 << 26))
+      return false;
+    if ((((int64_t)s->words[r] * 32) << s->shift[r]) < n[r]) return false;
+  }
+  return true;
+}
+inline SeedBitsK seed_bits_k(const mirec_seed_bits_t *s) {
+  return SeedBitsK{s->bits, (int32_t)s->split, s->shift[0], s->shift[1], s->words[0],
+                   s->words[1]};
+}
+
 // Row movers (gather / scatter / counted gather of [n, d] float rows): a
 // 256-thread block takes kRowRounds rounds of 256 >> lg rows, 1 << lg lanes
 // per row (lg = ceil log2 (d / 4); lanes past d / 4 idle), every thread

@@ -67,18 +67,27 @@ __device__ __forceinline__ int64_t key_node(int64_t i, const int32_t *keys, int6
                    : (i < 2 * batch ? n_users + pos[i - batch] : n_users + neg[i - 2 * batch]);
 }
 
+// The node's bit in the bit forms of S (mirec_seed_bits_t): an integer OR,
+// the same words in any order.
+__device__ __forceinline__ void set_seed_bit(const SeedBitsK &sb, int32_t node) {
+  const uint32_t pos = seed_bit_pos(sb, node);
+  atomicOr(sb.bits + (pos >> 5), 1u << (pos & 31u));
+}
+
 // One lane per key: S membership (first setter appends the node to the
-// deduplicated S list) and the node's own bm_hop byte.
+// deduplicated S list, and sets the node's bit in the bit forms of S when
+// they are asked for) and the node's own bm_hop byte.
 __global__ __launch_bounds__(256) void frontier_self_kernel(
     int64_t n_rows, const int32_t *__restrict__ keys, int64_t n_keys,
     const int32_t *__restrict__ users, const int32_t *__restrict__ pos,
     const int32_t *__restrict__ neg, int64_t batch, int64_t n_users, uint8_t *bm_self,
-    uint8_t *bm_hop, int32_t *self_list, int32_t *self_count) {
+    uint8_t *bm_hop, int32_t *self_list, int32_t *self_count, SeedBitsK sb) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t node = key_node(i, keys, n_keys, users, pos, neg, batch, n_users);
   const bool valid = node >= 0 && node < n_rows;  // empty / sentinel entries
   const bool first = valid && test_and_set(bm_self, node);
   if (valid) bm_hop[node] = 1;
+  if (first && sb.bits != nullptr) set_seed_bit(sb, (int32_t)node);
   const int32_t off = block_reserve(first ? 1 : 0, self_count);
   if (first) self_list[off] = (int32_t)node;
 }
@@ -117,7 +126,7 @@ __global__ __launch_bounds__(256) void frontier_keys_kernel(
     int32_t split, const int32_t *__restrict__ keys, int64_t n_keys,
     const int32_t *__restrict__ users, const int32_t *__restrict__ pos,
     const int32_t *__restrict__ neg, int64_t batch, int64_t n_users, uint8_t *bm_self,
-    uint8_t *bm_hop) {
+    uint8_t *bm_hop, SeedBitsK sb) {
   const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
   const int64_t node = key_node(i, keys, n_keys, users, pos, neg, batch, n_users);
@@ -125,6 +134,7 @@ __global__ __launch_bounds__(256) void frontier_keys_kernel(
   if (lane == 0) {
     bm_self[node] = 1;
     bm_hop[node] = 1;
+    if (sb.bits != nullptr) set_seed_bit(sb, (int32_t)node);
   }
   const int64_t beg = rowptr[node], end = rowptr[node + 1];
   if (split > 0 && end - beg > split) return;
@@ -668,7 +678,23 @@ extern "C" int mirec_frontier(const mirec_csr_t *c, const int32_t *keys, int64_t
                               uint8_t *bm_hop, int32_t *self_list, int32_t *self_count,
                               int32_t *zero_counts, int32_t n_zero_counts,
                               mirec_stream_t stream) {
+  return mirec_frontier_bits(c, keys, n_keys, users, pos, neg, batch, n_users, bm_self, bm_hop,
+                             self_list, self_count, zero_counts, n_zero_counts, nullptr, stream);
+}
+
+extern "C" size_t mirec_seed_bits_sizeof(void) { return sizeof(mirec_seed_bits_t); }
+
+extern "C" int mirec_frontier_bits(const mirec_csr_t *c, const int32_t *keys, int64_t n_keys,
+                                   const int32_t *users, const int32_t *pos, const int32_t *neg,
+                                   int64_t batch, int64_t n_users, uint8_t *bm_self,
+                                   uint8_t *bm_hop, int32_t *self_list, int32_t *self_count,
+                                   int32_t *zero_counts, int32_t n_zero_counts,
+                                   const mirec_seed_bits_t *bits, mirec_stream_t stream) {
   using namespace mirec;
+  MIREC_CHECK_ARG(c != nullptr && (bits == nullptr || seed_bits_valid(bits, c->n_rows)));
+  SeedBitsK sb = {};
+  if (bits != nullptr) sb = seed_bits_k(bits);
+  const size_t bit_bytes = 4 * ((size_t)sb.words0 + (size_t)sb.words1);
   MIREC_CHECK_ARG(c && c->rowptr && c->col && bm_self && bm_hop);
   MIREC_CHECK_ARG(keys != nullptr || (users && pos && neg && batch >= 0 && n_users >= 0));
   MIREC_CHECK_ARG(self_list == nullptr || self_count != nullptr);
@@ -679,8 +705,15 @@ extern "C" int mirec_frontier(const mirec_csr_t *c, const int32_t *keys, int64_t
   const size_t bytes16 = (bytes + 15) / 16 * 16;
   int32_t *sc = self_list != nullptr ? self_count : nullptr;
   if (bm_hop == bm_self + bytes16 && ((uintptr_t)bm_self & 15u) == 0) {
-    // adjacent, 16-B aligned maps: everything cleared by one launch
-    const int64_t n16 = (int64_t)(2 * bytes16 / 16);
+    // adjacent, 16-B aligned maps: everything cleared by one launch, the bit
+    // forms of S too when they follow the maps in whole 16-byte rows
+    int64_t n16 = (int64_t)(2 * bytes16 / 16);
+    if (bit_bytes > 0) {
+      if ((uint8_t *)sb.bits == bm_hop + bytes16 && bit_bytes % 16 == 0)
+        n16 += (int64_t)(bit_bytes / 16);
+      else
+        MIREC_HIP(hipMemsetAsync(sb.bits, 0, bit_bytes, st));
+    }
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n16 + 255) / 256, 1024));
     hipLaunchKernelGGL(frontier_clear_kernel, dim3(blocks), dim3(256), 0, st,
                        reinterpret_cast<uint4 *>(bm_self), n16, sc, zero_counts, n_zero_counts);
@@ -690,6 +723,7 @@ extern "C" int mirec_frontier(const mirec_csr_t *c, const int32_t *keys, int64_t
     MIREC_HIP(hipMemsetAsync(bm_hop, 0, bytes, st));
     if (sc != nullptr) MIREC_HIP(hipMemsetAsync(sc, 0, 4, st));
     if (n_zero_counts > 0) MIREC_HIP(hipMemsetAsync(zero_counts, 0, 4 * (size_t)n_zero_counts, st));
+    if (bit_bytes > 0) MIREC_HIP(hipMemsetAsync(sb.bits, 0, bit_bytes, st));
   }
   const int64_t n = keys != nullptr ? n_keys : 3 * batch;
   const int32_t split = c->n_seg > 0 ? c->split : 0;
@@ -697,7 +731,7 @@ extern "C" int mirec_frontier(const mirec_csr_t *c, const int32_t *keys, int64_t
     if (n > 0) {
       hipLaunchKernelGGL(frontier_self_kernel, dim3((n + 255) / 256), dim3(256), 0, st, c->n_rows,
                          keys, n_keys, users, pos, neg, batch, n_users, bm_self, bm_hop,
-                         self_list, self_count);
+                         self_list, self_count, sb);
       MIREC_LAUNCH_CHECK();
       hipLaunchKernelGGL(frontier_expand_kernel, dim3((n + kWaves - 1) / kWaves), dim3(256), 0,
                          st, c->rowptr, c->col, split, self_list, self_count, bm_hop);
@@ -706,7 +740,7 @@ extern "C" int mirec_frontier(const mirec_csr_t *c, const int32_t *keys, int64_t
   } else if (n > 0) {
     hipLaunchKernelGGL(frontier_keys_kernel, dim3((n + kWaves - 1) / kWaves), dim3(256), 0, st,
                        c->rowptr, c->col, c->n_rows, split, keys, n_keys, users, pos, neg, batch,
-                       n_users, bm_self, bm_hop);
+                       n_users, bm_self, bm_hop, sb);
     MIREC_LAUNCH_CHECK();
   }
   if (c->n_seg > 0 && n > 0) {

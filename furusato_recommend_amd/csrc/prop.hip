@@ -455,6 +455,217 @@ MIREC_NO_PK_F32 void prop_kernel(PropK a) {
   }
 }
 
+// ---- the seeded list launch (mirec_propagate_seeded): prop_kernel's list
+// mode for in_mode SPARSE without an in_mask, i.e. the first backward layer,
+// whose rows F1 = S ∪ N(S) hold ~23 entries per seeded one at C2.  There
+// prop_kernel is a chain of dependent loads per work item (list entry,
+// rowptr, col, slot[col], dinv[col] + seed row; the last four per chunk)
+// whose slot[col] test reads a 4.4 MB array for a 6 K-node set.  Here
+//   - the grid is the resident workgroups only, and each holds the bit forms
+//     of S (mirec_seed_bits_t, exact or coarsened: a superset) in LDS;
+//   - a work item issues its list entry's rowptr pair and row_mask byte
+//     together, then NR chunks of column loads back to back;
+//   - every column is tested against the LDS bits, and slot[col] and
+//     dinv[col] are loaded for the passing lanes only (the others read
+//     element 0 and drop it: every index-side load is unconditional), all
+//     chunks in one round;
+//   - the exact filter stays slot >= 0, and from there on a chunk is
+//     gather<.., SPARSE, MASKED, ..>'s: the same compaction inside the chunk
+//     of W entries, the same (k, u, grp) per compacted hit, the same fma
+//     order, combine_groups and row_epilogue, so the launch is bitwise
+//     prop_kernel's.
+// No waits on other workgroups, no atomics; work items in prop_kernel's
+// order (wide rows one per wave, then G narrow rows per wave).
+struct SeededK {
+  SeedBitsK bits;
+  int64_t last;  // nnz - 1 >= 0: column loads past a row's end are clamped to it
+};
+
+// Chunks per round (bounded by the registers the column, slot and dinv loads
+// of a round hold next to UNROLL float4 rows): 64-entry chunks of a wide row,
+// LPR-entry chunks of a narrow one.
+template <int D>
+constexpr int seeded_wide_chunks() {
+  return D >= 256 ? 2 : 4;
+}
+template <int D>
+constexpr int seeded_narrow_chunks() {
+  constexpr int n = 64 / (D / 4);
+  return n < 2 ? 2 : (n > 4 ? 4 : n);
+}
+
+// One chunk of gather<D, UNROLL, SPARSE, true, false, NARROW>: `cnt` entries,
+// this lane's entry being a hit iff myr (its slot) >= 0, myw = dinv of its
+// column.  Control flow is uniform over the lanes sharing the chunk.
+template <int D, int UNROLL, bool NARROW>
+__device__ __forceinline__ float4 seeded_chunk(const PropK &a, float4 acc, int cnt, int myr,
+                                               float myw, int lane) {
+  constexpr int LPR = D / 4;
+  constexpr int G = 64 / LPR;
+  constexpr int W = NARROW ? LPR : 64;
+  const int grp = lane / LPR;
+  const int sub = lane % LPR;
+  const int l0 = NARROW ? grp * LPR : 0;
+  const int me = NARROW ? sub : lane;
+  const bool ok = myr >= 0;
+  const unsigned long long bal = __ballot(ok);
+  const unsigned long long m = (W == 64) ? bal : ((bal >> l0) & ((1ull << (W & 63)) - 1ull));
+  const int nv = __popcll(m);
+  if (nv == 0) return acc;
+  if (nv < cnt) {  // compact the hits to the front
+    const int below = __popcll(m & ((1ull << me) - 1ull));
+    const int dst = l0 + (ok ? below : nv + (me - below));
+    myr = __builtin_amdgcn_ds_permute(dst << 2, myr);
+    myw = __int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int(myw)));
+  }
+  if (myr < 0) {  // a lane past the hits: never gathered, its weight multiplies a zero row
+    myr = 0;
+    myw = 0.f;
+  }
+  for (int k = 0; k < nv; k += (NARROW ? 1 : G) * UNROLL) {
+    float4 v[UNROLL];
+    float w[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const int idx = NARROW ? k + u : k + u * G + grp;
+      const int srcl = l0 + (idx & (W - 1));
+      const int j = __shfl(myr, srcl);
+      w[u] = __shfl(myw, srcl);
+      if (idx < nv)
+        v[u] = ld4(a.seed_in + (int64_t)j * D + sub * 4);
+      else
+        v[u] = f4_zero();
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) acc = f4_fma(w[u], v[u], acc);
+  }
+  return acc;
+}
+
+// The `deg` entries from `beg` of a row (NARROW: of this lane group's row) in
+// `rounds` rounds of NR chunks (wave-uniform; rounds * NR chunks cover the
+// longest row of the wave).  Offsets into the row are 32-bit; a column load
+// past the row's end is clamped to the CSR's last entry and dropped.
+template <int D, int UNROLL, bool NARROW, int NR>
+__device__ __forceinline__ float4 gather_seeded(const PropK &a, const SeededK &f,
+                                                const uint32_t *bits, int64_t beg, int deg,
+                                                int rounds, int lane) {
+  constexpr int LPR = D / 4;
+  constexpr int W = NARROW ? LPR : 64;
+  const int me = NARROW ? lane % LPR : lane;
+  const int32_t *cp = a.col + beg;
+  const int lim = (int)min(f.last - beg, (int64_t)0x7fffffff);  // (-1: col[beg - 1] = col[last])
+  float4 acc = f4_zero();
+#pragma unroll 1
+  for (int it = 0, off = me; it < rounds; ++it, off += NR * W) {
+    int c[NR], s[NR];
+    float w[NR];
+    bool pass[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) c[r] = cp[min(off + r * W, lim)];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const uint32_t pos = seed_bit_pos(f.bits, c[r]);
+      pass[r] = off + r * W < deg && ((bits[pos >> 5] >> (pos & 31u)) & 1u) != 0u;
+      const int j = pass[r] ? c[r] : 0;
+      s[r] = a.slot[j];
+      w[r] = a.dinv[j];
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int cnt = max(0, min(W, deg - (off - me + r * W)));
+      acc = seeded_chunk<D, UNROLL, NARROW>(a, acc, cnt, pass[r] ? s[r] : -1, w[r], lane);
+    }
+  }
+  return acc;
+}
+
+// One row by one wave (prop_kernel's wave_row / the walk of a wave that holds
+// a long row).
+template <int D, int UNROLL>
+__device__ __forceinline__ void seeded_wave_row(const PropK &a, const SeededK &f,
+                                                const uint32_t *bits, int32_t row, int64_t beg,
+                                                int deg, int lane) {
+  constexpr int LPR = D / 4;
+  constexpr int NRW = seeded_wide_chunks<D>();
+  const int rounds = __builtin_amdgcn_readfirstlane((deg + NRW * 64 - 1) / (NRW * 64));
+  float4 s = gather_seeded<D, UNROLL, false, NRW>(a, f, bits, beg, deg, rounds, lane);
+  s = combine_groups<D>(s);
+  if (lane < LPR) row_epilogue<D>(a, row, s, lane % LPR);
+}
+
+// (the body is a separate always-inline function, as the sweep kernels': the
+// shuffle and ballot wrappers inline into it, and it into the kernel)
+template <int D, int UNROLL>
+__device__ __forceinline__ void seeded_work(const PropK &a, const SeededK &f) {
+  constexpr int LPR = D / 4;
+  constexpr int G = 64 / LPR;
+  constexpr int NARROW_UNROLL = UNROLL < 4 ? 4 : UNROLL;
+  constexpr int NRN = seeded_narrow_chunks<D>();
+  extern __shared__ uint32_t seeded_bits[];
+  const int n_words = f.bits.words0 + f.bits.words1;
+  for (int i = threadIdx.x; i < n_words; i += 256) seeded_bits[i] = f.bits.bits[i];
+  __syncthreads();
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t n_wide = a.wide_list != nullptr ? (int64_t)*a.wide_count : 0;
+  const int64_t wide_blocks = (n_wide + kWavesPerBlock - 1) / kWavesPerBlock;
+  const int64_t nrows = *a.row_count;
+  const int64_t row_waves = (nrows + G - 1) / G;
+  const int64_t total = wide_blocks + (row_waves + kWavesPerBlock - 1) / kWavesPerBlock;
+#pragma unroll 1
+  for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
+    // The lane index is made opaque per work item: everything derived from it
+    // (lane masks, the per-lane offsets into a dozen operand pointers) is then
+    // recomputed here instead of being hoisted out of the loop, where those
+    // values held more registers across a work item than the file has
+    // (spills to scratch).
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
+    lane &= 63;  // (its range, known again: the shuffles' operands keep their known bits)
+    const int sub = lane % LPR;
+    const int grp = lane / LPR;
+    if (b < wide_blocks) {
+      const int64_t i = b * kWavesPerBlock + wid;
+      if (i >= n_wide) continue;  // wave-uniform
+      const int32_t row = a.wide_list[i];
+      const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
+      seeded_wave_row<D, UNROLL>(a, f, seeded_bits, row, beg, (int)(end - beg), lane);
+      continue;
+    }
+    const int64_t w = (b - wide_blocks) * kWavesPerBlock + wid;
+    if (w >= row_waves) continue;  // wave-uniform
+    const int64_t idx = w * G + grp;
+    bool have = idx < nrows;
+    const int32_t row = a.row_list[have ? idx : 0];
+    const int64_t beg = a.rowptr[row], end = a.rowptr[row + 1];
+    have = have && a.row_mask[row] != 0;
+    const int deg = have ? (int)(end - beg) : 0;
+    if (G > 1 && __ballot(deg > a.narrow_max) == 0ull) {
+      int rounds = (deg + NRN * LPR - 1) / (NRN * LPR);
+#pragma unroll
+      for (int m = LPR; m < 64; m <<= 1) rounds = max(rounds, __shfl_xor(rounds, m));
+      rounds = __builtin_amdgcn_readfirstlane(rounds);
+      float4 s = gather_seeded<D, NARROW_UNROLL, true, NRN>(a, f, seeded_bits, beg, deg, rounds,
+                                                            lane);
+      if (have) row_epilogue<D>(a, row, s, sub);
+    } else {
+#pragma unroll 1
+      for (int g = 0; g < G; ++g) {
+        const int src = g * LPR;
+        if (!__shfl((int)have, src)) continue;  // wave-uniform
+        seeded_wave_row<D, UNROLL>(a, f, seeded_bits, __shfl(row, src),
+                                   __shfl((long long)beg, src), __shfl(deg, src), lane);
+      }
+    }
+  }
+}
+
+template <int D, int UNROLL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8)))
+MIREC_NO_PK_F32 void prop_seeded_kernel(PropK a, SeededK f) {
+  seeded_work<D, UNROLL>(a, f);
+}
+
 // One workgroup per long row: its NG = 256 / LPR lane groups sum the
 // segments sg0 + k, sg0 + k + NG, ... (group k, 4 partial rows in flight),
 // then group 0 adds the NG group sums in order and runs the epilogue.  A
@@ -985,6 +1196,42 @@ static int launch_prop(const mirec_csr_t *c, PropK k, int64_t list_cap, int mode
   return MIREC_OK;
 }
 
+// The seeded list launch: as many workgroups as stay resident with the bit
+// arrays in LDS (asked of the runtime once per array size), or fewer when
+// the lists cannot hold that much work.
+constexpr size_t kSeededLdsMax = 64 * 1024;
+
+template <int D, int UNROLL>
+static int launch_seeded(PropK k, const mirec_seed_bits_t *sb, int64_t nnz, int64_t list_cap,
+                         hipStream_t st) {
+  constexpr int G = 64 / (D / 4);
+  SeededK f;
+  f.bits = seed_bits_k(sb);
+  f.last = nnz - 1;
+  const size_t lds = 4 * ((size_t)f.bits.words0 + (size_t)f.bits.words1);
+  const auto kernel = prop_seeded_kernel<D, UNROLL>;
+  static thread_local size_t cached_lds = 0;
+  static thread_local int64_t cached_resident = 0;
+  if (cached_resident == 0 || cached_lds != lds) {
+    int dev = 0, cus = 0, per_cu = 0;
+    MIREC_HIP(hipGetDevice(&dev));
+    MIREC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    MIREC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &per_cu, reinterpret_cast<const void *>(kernel), 256, lds));
+    cached_resident = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
+    cached_lds = lds;
+  }
+  const int64_t row_waves = (list_cap + G - 1) / G;
+  int64_t blocks = (row_waves + kWavesPerBlock - 1) / kWavesPerBlock;
+  if (k.wide_list != nullptr) blocks += (list_cap + kWavesPerBlock - 1) / kWavesPerBlock;
+  blocks = std::min(blocks, cached_resident);
+  if (blocks > 0) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), lds, st, k, f);
+    MIREC_LAUNCH_CHECK();
+  }
+  return MIREC_OK;
+}
+
 // x~ = dinv ⊙ x (row scale), float4.
 __global__ __launch_bounds__(256) void prescale_kernel(const float *__restrict__ x,
                                                        const float *__restrict__ dinv, int64_t n4,
@@ -1227,7 +1474,8 @@ static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sw
                      const mirec_sweep_wave_t *wi, const mirec_sweep_wave_t *wu,
                      mirec_stream_t stream, const mirec_drop_t *drop = nullptr,
                      const mirec_sweep_pace_t *pace = nullptr,
-                     const SweepStamp *stamp = nullptr) {
+                     const SweepStamp *stamp = nullptr,
+                     const mirec_seed_bits_t *seeded = nullptr) {
   MIREC_CHECK_ARG(c != nullptr && p != nullptr);
   if (pace != nullptr) {
     MIREC_CHECK_ARG(pace->ws != nullptr);
@@ -1333,6 +1581,21 @@ static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sw
     if (sweep_wave_valid(c, wu, 0, wi->row0)) return launch_sweep_wave<64>(k, wu, st, pace, 1);
     return launch_head<64, 4>(c, k, wi->row0, st);
   }
+  if (seeded != nullptr) {  // (a launch of the seeded shape: mirec_propagate_seeded)
+    switch (p->dim) {
+      case 4: return launch_seeded<4, 1>(k, seeded, c->nnz, cap, st);
+      case 8: return launch_seeded<8, 1>(k, seeded, c->nnz, cap, st);
+      case 16: return launch_seeded<16, 1>(k, seeded, c->nnz, cap, st);
+      case 32: return launch_seeded<32, 2>(k, seeded, c->nnz, cap, st);
+      case 64: return launch_seeded<64, 4>(k, seeded, c->nnz, cap, st);
+      case 128: return launch_seeded<128, 4>(k, seeded, c->nnz, cap, st);
+      // (UNROLL batches the row loads only: hit idx of a chunk goes to group
+      // idx % G and a group adds its hits in ascending idx whatever UNROLL is;
+      // 4 rows per batch keep the 256-wide kernel free of spills)
+      case 256: return launch_seeded<256, 4>(k, seeded, c->nnz, cap, st);
+    }
+    return MIREC_ERR_DIM;
+  }
   switch (p->dim) {
     case 4: return launch_prop<4, 1>(c, k, cap, p->in_mode, st, dropout);
     case 8: return launch_prop<8, 1>(c, k, cap, p->in_mode, st, dropout);
@@ -1390,6 +1653,21 @@ extern "C" size_t mirec_drop_sizeof(void) { return sizeof(mirec_drop_t); }
 extern "C" int mirec_propagate_drop(const mirec_csr_t *c, const mirec_prop_t *p,
                                     const mirec_drop_t *drop, mirec_stream_t stream) {
   return mirec::propagate(c, p, nullptr, nullptr, nullptr, stream, drop);
+}
+
+extern "C" int mirec_propagate_seeded(const mirec_csr_t *c, const mirec_prop_t *p,
+                                      const mirec_seed_bits_t *filter, mirec_stream_t stream) {
+  using namespace mirec;
+  MIREC_CHECK_ARG(c != nullptr && p != nullptr);
+  const bool shape = filter != nullptr && p->in_mode == MIREC_IN_SPARSE &&
+                     p->row_list != nullptr && p->in_mask == nullptr && c->val == nullptr &&
+                     c->n_seg == 0 && c->nnz > 0 && p->scale_src == nullptr &&
+                     p->scale_dst == nullptr && p->scale_next == nullptr;
+  if (!shape) return mirec_propagate(c, p, stream);
+  MIREC_CHECK_ARG(seed_bits_valid(filter, c->n_rows));
+  const size_t lds = 4 * ((size_t)filter->words[0] + (size_t)filter->words[1]);
+  if (lds == 0 || lds > kSeededLdsMax) return mirec_propagate(c, p, stream);
+  return propagate(c, p, nullptr, nullptr, nullptr, stream, nullptr, nullptr, nullptr, filter);
 }
 
 extern "C" int mirec_edge_keep_mask(const int64_t *rowptr, const int32_t *col, int64_t n_rows,

@@ -5,7 +5,9 @@ top of ``bpr_loss`` :98-118 and ``forward`` :78-86) runs as ~2L+8 HIP
 launches with no host synchronisation:
 
   frontier (3-4)          S = batch nodes, F1 = S ∪ N(S) as byte maps and
-                          row lists
+                          row lists; S also as two bit arrays (users, items;
+                          exact or coarsened to an LDS budget) set by the
+                          same launches, for the first backward layer
   forward  (L [+1])       x~_0 = dinv ⊙ E (skipped when the previous step's
                           fused update already wrote it), x_l = Â x_{l-1};
                           acc = x_0 + ... + x_L; out = acc/(L+1).  Every
@@ -22,7 +24,11 @@ launches with no host synchronisation:
                           destination scales swapped, see _prop).  The first
                           backward layer gathers only the seeded
                           neighbours (IN_SPARSE: slot[j] >= 0) and
-                          is written on F1 only; the second skips neighbours
+                          is written on F1 only (seeded_first, L >= 2 on a
+                          plain bipartite graph: a persistent kernel that
+                          tests every neighbour against the bits of S in LDS
+                          and reads slot[j] of the passing ones only, bitwise
+                          the same result); the second skips neighbours
                           outside F1; the last one adds the reg seed and
                           applies Adam to E in its epilogue, so the dense
                           gradient is never written to HBM; it also writes
@@ -59,6 +65,36 @@ SWEEP_USERS = True
 # (None, or a dict(lead_bands, every, nap) per block "items" / "users").
 LAYER_SUM_ROWS = "self"
 SWEEP_PACE = {"items": (8, 16, 16), "users": (4, 4, 16)}
+# Defaults of PropagationEngine.seeded_first and seeded_lds_bytes (DESIGN.md
+# §24): 16 KB for both bit arrays keeps 8 workgroups per CU resident.
+SEEDED_FIRST = True
+SEEDED_LDS_BYTES = 16 * 1024
+
+
+def seed_bit_layout(n0: int, n1: int, budget: int):
+    """(shifts, words) of the two bit arrays of mirec_seed_bits_t for ranges
+    of n0 and n1 nodes under an LDS budget in bytes: the smaller range takes
+    the smallest shift at which its array fits 7/8 of the budget, the larger
+    one the smallest at which it fits what is left (one word at the least).
+    The second array is padded so that both together are whole 16-byte rows
+    (cleared by the frontier's one clear launch)."""
+    def words(n, s):
+        return -(-(-(-n // (1 << s))) // 32)
+
+    def fit(n, share):
+        s = 0
+        while s < 31 and words(n, s) > 1 and 4 * words(n, s) > share:
+            s += 1
+        return s
+    n = (int(n0), int(n1))
+    small = 0 if n[0] <= n[1] else 1
+    shift, w = [0, 0], [0, 0]
+    shift[small] = fit(n[small], int(budget) * 7 // 8)
+    w[small] = words(n[small], shift[small])
+    shift[1 - small] = fit(n[1 - small], int(budget) - 4 * w[small])
+    w[1 - small] = words(n[1 - small], shift[1 - small])
+    w[1] += -(w[0] + w[1]) % 4
+    return tuple(shift), tuple(w)
 
 
 def prop_launch_bytes(in_mode: int, n_nodes: int, nnz: int, dim: int, *, slot=False,
@@ -301,9 +337,14 @@ class PropagationEngine:
             [torch.empty(N, D, **f32)] if self.L == 1 else []
         self.slot = torch.full((N,), -1, **i32)
         words = (N + 15) // 16 * 4  # 16-byte rows (mask_compact reads 16 B per thread)
-        # S and S ∪ N(S) byte maps (int32-backed), adjacent: cleared together
-        self._bm = torch.zeros(2, words, **i32)
-        self.bm_self, self.bm_hop = self._bm[0], self._bm[1]
+        # S and S ∪ N(S) byte maps (int32-backed), adjacent: cleared together;
+        # behind them the bit forms of S (seeded_first) at their
+        # largest (shift 0), so that the frontier's one clear covers them too
+        nu = graph.n_users if graph.m_items > 0 else N
+        self._bit_cap = (-(-nu // 32), -(-(N - nu) // 32))
+        self._bm = torch.zeros(2 * words + (sum(self._bit_cap) + 3) // 4 * 4, **i32)
+        self.bm_self, self.bm_hop = self._bm[:words], self._bm[words:2 * words]
+        self._seed_bits_mem = self._bm[2 * words:]
         # S, deduplicated
         B3 = max((2 + self.n_neg) * self.max_batch, 2 * self.max_batch + self.n_shared)
         self.self_list = torch.zeros(B3, **i32)
@@ -344,6 +385,14 @@ class PropagationEngine:
         # hits), "dense" (seed rows scattered into a zero [N, D] table and
         # gathered as a byte-map-filtered PRESCALED input) or "auto"
         self.sparse_filter = "auto"
+        # the first backward layer's list launch through the LDS-prefiltered
+        # kernel (mirec_propagate_seeded; graphs and steps that
+        # do not qualify run the launch above, bit for bit) and the LDS budget
+        # of its two bit arrays
+        self.seeded_first = SEEDED_FIRST
+        self._seeded_lds_bytes = SEEDED_LDS_BYTES
+        self._seed_bits = None
+        self._bits_ready = False
         self._masks_ready = False
         # rows of degree <= narrow_max are gathered one per lane group
         self.narrow_max = 64
@@ -451,8 +500,12 @@ class PropagationEngine:
     def _prop(self, *, in_mode, x_in=None, seed_in=None, seed=None, addend=None, seed2=None,
               divisor=1.0, out=None, xs_out=None, adam=None, param=None, graph=None,
               row_mask=None, in_mask=None, row_list=None, row_count=None, row_list_cap=0,
-              out_mask=None, wide_list=None, wide_count=None, direction="fwd", stamp=None):
-        """One propagation launch.  ``direction`` matters on an r-adjusted
+              out_mask=None, wide_list=None, wide_count=None, direction="fwd", stamp=None,
+              seeded=False):
+        """One propagation launch.  ``seeded``: the first backward layer's list
+        launch through mirec_propagate_seeded and the step's bit arrays (its
+        filter is slot >= 0, which an ``in_mask`` over S selects too: the
+        launch gets none, the timing key keeps it).  ``direction`` matters on an r-adjusted
         graph only (scales a = deg^-r, b = deg^-(1-r); otherwise the three
         scale pointers stay NULL = dinv): "fwd" applies Â = D_b A D_a and
         writes xs_out = a ⊙ z; "bwd" applies Âᵀ = D_a A D_b and writes
@@ -517,6 +570,11 @@ class PropagationEngine:
                              seed=self._drop[1])
             check(lib.mirec_propagate_drop(g.csr_ptr(), ctypes.byref(p), ctypes.byref(drop),
                                            _lib.stream_handle()), "propagate_drop")
+        elif seeded:
+            p.in_mask = None
+            check(lib.mirec_propagate_seeded(g.csr_ptr(), ctypes.byref(p),
+                                             ctypes.byref(self._seed_bits_struct()),
+                                             _lib.stream_handle()), "propagate_seeded")
         elif on and self._sweep_form == "wave":
             wi, wu = self.sweep_wave, self.sweep_wave_users if self._sweep_users else None
             pace = self._pace_struct()
@@ -588,26 +646,29 @@ class PropagationEngine:
         # the frontier's clear launch (one launch for maps, S count, counters)
         lists = self.prune and self.use_hop_list
         zc, nz = (self.list_counts.data_ptr(), 4) if lists else (None, 0)
+        # the bit forms of S for the first backward layer, by the same launches
+        sb = ctypes.byref(self._seed_bits_struct()) if self._seeded_ok() else None
         if keys is not None:
             n = int(n_keys)
             if self.self_list.shape[0] < n:
                 self.self_list = torch.zeros(n, dtype=torch.int32, device=g.device)
-            check(lib.mirec_frontier(g.csr_ptr(), keys.data_ptr(), n, None, None, None,
-                                     0, g.n_users, self.bm_self.data_ptr(),
-                                     self.bm_hop.data_ptr(), self.self_list.data_ptr(),
-                                     self.self_count.data_ptr(), zc, nz, _lib.stream_handle()),
-                  "frontier")
+            check(lib.mirec_frontier_bits(g.csr_ptr(), keys.data_ptr(), n, None, None, None,
+                                          0, g.n_users, self.bm_self.data_ptr(),
+                                          self.bm_hop.data_ptr(), self.self_list.data_ptr(),
+                                          self.self_count.data_ptr(), zc, nz, sb,
+                                          _lib.stream_handle()), "frontier")
             self._self_cap = n
         else:
             B = int(users.shape[0])
             if B > self.max_batch:
                 raise ValueError(f"batch {B} > engine max_batch {self.max_batch}")
-            check(lib.mirec_frontier(g.csr_ptr(), None, 0, users.data_ptr(), pos.data_ptr(),
-                                     neg.data_ptr(), B, g.n_users,
-                                     self.bm_self.data_ptr(), self.bm_hop.data_ptr(),
-                                     self.self_list.data_ptr(), self.self_count.data_ptr(),
-                                     zc, nz, _lib.stream_handle()), "frontier")
+            check(lib.mirec_frontier_bits(g.csr_ptr(), None, 0, users.data_ptr(), pos.data_ptr(),
+                                          neg.data_ptr(), B, g.n_users,
+                                          self.bm_self.data_ptr(), self.bm_hop.data_ptr(),
+                                          self.self_list.data_ptr(), self.self_count.data_ptr(),
+                                          zc, nz, sb, _lib.stream_handle()), "frontier")
             self._self_cap = 3 * B
+        self._bits_ready = sb is not None
         if lists:
             # S and F1 compacted in one launch, the degree split from a static
             # bitmap (mirec_mask_compact_pair; counters zeroed by the frontier)
@@ -721,6 +782,47 @@ class PropagationEngine:
         if f == "auto":
             f = "bytemap" if self._self_cap > (2 + self.n_neg) * self.max_batch else "slot"
         return self.bm_self if f == "bytemap" else None
+
+    @property
+    def seeded_lds_bytes(self) -> int:
+        """LDS budget of the seeded launch's two bit arrays (tuning; tests
+        force coarse and exact arrays with it)."""
+        return self._seeded_lds_bytes
+
+    @seeded_lds_bytes.setter
+    def seeded_lds_bytes(self, nbytes: int):
+        if int(nbytes) < 8:
+            raise ValueError(f"seeded_lds_bytes: at least 8, got {nbytes!r}")
+        self._seeded_lds_bytes = int(nbytes)
+        self._seed_bits = None
+        self._bits_ready = False  # the arrays in memory have the old shifts
+
+    def seed_bit_shifts(self):
+        """(user range, item range) shifts of the bit arrays."""
+        sb = self._seed_bits_struct()
+        return sb.shift[0], sb.shift[1]
+
+    def _seed_bits_struct(self):
+        if self._seed_bits is None:
+            g = self.g
+            nu = g.n_users if g.m_items > 0 else g.n_nodes
+            shift, words = seed_bit_layout(nu, g.n_nodes - nu, self._seeded_lds_bytes)
+            sb = _lib.SeedBits(bits=self._seed_bits_mem.data_ptr(), split=nu)
+            sb.shift[0], sb.shift[1] = shift
+            sb.words[0], sb.words[1] = words
+            self._seed_bits = sb
+        return self._seed_bits
+
+    def _seeded_ok(self) -> bool:
+        """Does this engine's first backward layer take the seeded launch?
+        L >= 2, pruned with row lists, a bipartite from_interactions graph
+        with neither long-row segments, edge values nor r-adjusted scales, no
+        edge dropout in force."""
+        g = self.g
+        return bool(self.seeded_first and self.L >= 2 and self.prune and self.use_hop_list
+                    and self.sparse_filter != "dense" and g.n_users > 0 and g.m_items > 0
+                    and g._coo is None and g.n_seg == 0 and g.val is None
+                    and g.scale_src is None and self._drop is None)
 
     def static_row_lists(self, bm: torch.Tensor) -> dict:
         """Launch arguments restricting a propagation to the rows whose byte in
@@ -1101,6 +1203,8 @@ class PropagationEngine:
                     else:
                         kw = dict(in_mode=IN_SPARSE, seed_in=seed_p,
                                   in_mask=self._sparse_filter(), **rows)
+                        if l > 0 and self._bits_ready and self._seeded_ok():
+                            kw["seeded"] = True
                 else:
                     kw = dict(in_mode=IN_PRESCALED, x_in=self.xs[(L - 2 - l) % 2],
                               in_mask=self.bm_hop if (self.prune and l == L - 2) else None)
@@ -1115,7 +1219,7 @@ class PropagationEngine:
         check(lib.mirec_bpr_seed_reset(self.slot.data_ptr(), keys_sorted.data_ptr(), n_keys,
                                        _lib.stream_handle()), "bpr_seed_reset")
         self._seeds = None
-        self._masks_ready = False
+        self._masks_ready = self._bits_ready = False
         self._x0s_token = self._token(emb) if (adam is not None and L > 0 and last_rows is None
                                                and self.reuse_prescaled) else None
 

@@ -524,6 +524,46 @@ int mirec_frontier(const mirec_csr_t *csr, const int32_t *keys, int64_t n_keys,
                    uint8_t *bm_hop, int32_t *self_list, int32_t *self_count,
                    int32_t *zero_counts, int32_t n_zero_counts, mirec_stream_t stream);
 
+/* Bit forms of a seed set S for the first backward layer's LDS prefilter
+ * (mirec_propagate_seeded).  The nodes [0, split) and [split, n_rows) (users
+ * and items of a bipartite graph) have an array each, range 0 first: bit
+ * (node - range base) >> shift[r] of range r is set iff some node of S maps
+ * to it, so shift 0 is S itself and a larger shift a superset of it.
+ * `bits`: words[0] + words[1] device words, 4-byte aligned; words[r] * 32
+ * bits must cover range r at shift[r] (MIREC_ERR_ARG otherwise). */
+typedef struct mirec_seed_bits {
+  uint32_t *bits;
+  int64_t split;
+  int32_t shift[2];
+  int32_t words[2];
+} mirec_seed_bits_t;
+
+size_t mirec_seed_bits_sizeof(void);
+
+/* mirec_frontier that also fills `sb` for the same S, with no launch more:
+ * the words are cleared with the maps (by the one clear launch when sb->bits
+ * starts right after bm_hop's 16-byte-rounded size and words[0] + words[1] is
+ * a multiple of 4) and set with integer atomicOr by the lanes that set
+ * bm_self.  sb == NULL is exactly mirec_frontier. */
+int mirec_frontier_bits(const mirec_csr_t *csr, const int32_t *keys, int64_t n_keys,
+                        const int32_t *users, const int32_t *pos, const int32_t *neg,
+                        int64_t batch, int64_t n_users, uint8_t *bm_self,
+                        uint8_t *bm_hop, int32_t *self_list, int32_t *self_count,
+                        int32_t *zero_counts, int32_t n_zero_counts,
+                        const mirec_seed_bits_t *sb, mirec_stream_t stream);
+
+/* mirec_propagate for the list launch of the first backward layer (in_mode =
+ * MIREC_IN_SPARSE with row lists, no in_mask), bit for bit: a persistent grid
+ * whose workgroups hold `filter`'s bits in LDS, test every column against
+ * them and read slot[col] of the passing ones only; the terms of a row are
+ * the columns with slot >= 0, in mirec_propagate's order.  `filter` must
+ * hold a superset of {v : slot[v] >= 0} (mirec_frontier_bits of the keys the
+ * seeds were made from).  A launch of any other shape (another in_mode, no
+ * row lists, an in_mask, edge values, scale vectors, long-row segments, bit
+ * arrays beyond 64 KB) or filter == NULL runs mirec_propagate itself. */
+int mirec_propagate_seeded(const mirec_csr_t *csr, const mirec_prop_t *p,
+                           const mirec_seed_bits_t *filter, mirec_stream_t stream);
+
 /* mirec_mask_compact of two byte maps in one launch (the step's S and F1 =
  * S ∪ N(S)), the degree split read from wide_bits (bit v of word v / 32:
  * degree of node v > narrow_max; built once per graph) instead of rowptr:

@@ -36,6 +36,10 @@ VARIANTS = {
     "sweep_pace_on": {"sweep_pace": {"items": (8, 16, 16), "users": (4, 4, 16)}},
     "layer_sum_hop": {"layer_sum_rows": "hop"},
     "layer_sum_self": {"layer_sum_rows": "self"},
+    # the first backward layer through the LDS-prefiltered list kernel
+    # 
+    "seeded_first_off": {"seeded_first": False},
+    "seeded_first_on": {"seeded_first": True},
 }
 
 
