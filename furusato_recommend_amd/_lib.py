@@ -304,6 +304,10 @@ SIGNATURES = {
                                        c_int64, c_void_p]),
     "mirec_csr_tattn": (c_int, [POINTER(CSR), c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                 c_int64, c_int32, c_int32, c_float, c_void_p, c_void_p]),
+    "mirec_gru_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
+                               c_void_p]),
+    "mirec_gru_gate_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mirec_row_grad_group_size": (c_int64, []),
     "mirec_table_grad_workspace": (c_int, [POINTER(RowGradGroup), c_int32, c_int32, c_int32,
                                            POINTER(c_size_t)]),

@@ -1,6 +1,7 @@
 """Model registry with the reference's names (main.py:32-56, subset on the
 hot path: 'lgn' = LightGCN, 'lgnssm' = LightGCNSSM, 'radj' = rAdjGCN,
-'mf' = MF, 'sage' = GraphSAGE, 'gnn' = GNN with conv = 'gat', 'tgrec' = TGRec
+'mf' = MF, 'sage' = GraphSAGE, 'gnn' = GNN with conv = 'gat' (GATConv hops,
+the default) or 'ggnn' (GatedGraphConv hops), 'tgrec' = TGRec
 (TransformerConv hops), 'sasrec' = SASRec)."""
 from .gnn import GNN
 from .graphsage import GraphSAGE

@@ -1187,6 +1187,34 @@ int mirec_csr_tattn(const mirec_csr_t *csr, const float *query, const float *ski
                     const float *key, const float *value, int64_t ld_kv,
                     int32_t heads, int32_t ch, float scale, float *out, mirec_stream_t stream);
 
+/* GRU gate of the gated graph hop (PyG GatedGraphConv(d, num_layers=1,
+ * aggr='mean'), model/gnn.py conv = 'ggnn': a GRUCell on (mean of the
+ * projected children, the node's own row)).  gi = a W_ihᵀ + b_ih and gh = h
+ * W_hhᵀ + b_hh are finished pre-activations, [n_rows, 3 dim] with the thirds
+ * in the order r, z, n (the biases are the GEMMs' business); h [n_rows, dim]:
+ *   r = sigmoid(gi_r + gh_r)   z = sigmoid(gi_z + gh_z)
+ *   n = tanh(gi_n + r gh_n)    out = (1 - z) n + z h   (max(., 0) if relu)
+ * sigmoid and tanh saturate: every finite pre-activation gives a finite out.
+ * All tensors contiguous, dim % 4 == 0, 4 <= dim <= 1024, every pointer
+ * 16-byte aligned; anything else is MIREC_ERR_ARG, nothing launched.  n_rows
+ * == 0 is MIREC_OK. */
+int mirec_gru_gate(const float *gi, const float *gh, const float *h, int64_t n_rows,
+                   int32_t dim, int32_t relu, float *out, mirec_stream_t stream);
+
+/* Backward of mirec_gru_gate.  The gates are recomputed from gi, gh, h; out
+ * (the forward's output) is read only for the ReLU mask, g = grad_out where
+ * out > 0 and 0 elsewhere — NULL if the forward ran without relu.
+ *   dn = g (1 - z)   dz = g (h - n)   pn = dn (1 - n^2)
+ *   grad_gi_n = pn   grad_gh_n = pn r   dr = pn gh_n
+ *   grad_gi_r = grad_gh_r = dr r (1 - r)   grad_gi_z = grad_gh_z = dz z (1 - z)
+ *   grad_h = g z     (the direct path only; the one through gh is the GEMM's)
+ * All three are plain stores, written, not added to: no atomics, the same
+ * bits from run to run.  The bias gradients are the column sums of grad_gi
+ * and grad_gh (mirec_col_sums).  Limits as the forward. */
+int mirec_gru_gate_bwd(const float *grad_out, const float *gi, const float *gh, const float *h,
+                       const float *out, int64_t n_rows, int32_t dim, float *grad_gi,
+                       float *grad_gh, float *grad_h, mirec_stream_t stream);
+
 /* Deterministic id-table gradient (model/graphsage.py:311-337) and the Adam
  * step that consumes it (graphsage.py:388-397).  The table gradient of one
  * step is G[r] = c[slice(r)] * table[r] + S[r]: c = (c_user, c_item) the
