@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("MIREC_LIB") or os.path.join(_HERE, "libmirec.so")
 
 MIREC_OK = 0
 ERR_WORKSPACE = 4  # MIREC_ERR_WORKSPACE
+ERR_RANGE = 5  # MIREC_ERR_RANGE
 IN_PRESCALED, IN_RAW, IN_SPARSE, IN_NONE = 0, 1, 2, 3
 SUPPORTED_DIMS = (4, 8, 16, 32, 64, 128, 256)
 
@@ -61,7 +62,7 @@ class Prop(Structure):
         ("adam", AdamH), ("partial", c_void_p), ("row_mask", c_void_p),
         ("in_mask", c_void_p), ("out_mask", c_void_p), ("row_list", c_void_p),
         ("row_count", c_void_p),
-        ("row_list_cap", c_int64), ("narrow_max", c_int32), ("_pad2", c_int32),
+        ("row_list_cap", c_int64), ("narrow_max", c_int32), ("adam_stream", c_int32),
         ("wide_list", c_void_p), ("wide_count", c_void_p),
         ("scale_src", c_void_p), ("scale_dst", c_void_p), ("scale_next", c_void_p),
     ]
@@ -94,7 +95,7 @@ class SweepWave(Structure):
         ("row0", c_int64), ("n_rows", c_int64), ("src0", c_int64), ("n_src", c_int64),
         ("n_slots", c_int64),
         ("tile_rows", c_int32), ("wave_rows", c_int32), ("n_tiles", c_int32),
-        ("band_rows", c_int32), ("grid", c_int32), ("_pad", c_int32),
+        ("band_rows", c_int32), ("grid", c_int32), ("row_bits", c_int32),
         ("wptr", c_void_p), ("slot", c_void_p),
     ]
 
@@ -151,6 +152,8 @@ SIGNATURES = {
     "mirec_sweep_wave_sizeof": (c_size_t, []),
     "mirec_sweep_wave_build": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                        c_int32, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
+    "mirec_sweep_wave_pack": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p,
+                                      POINTER(c_int32)]),
     "mirec_propagate_sweep_wave": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(SweepWave),
                                            POINTER(SweepWave), c_void_p]),
     "mirec_sweep_pace_sizeof": (c_size_t, []),

@@ -382,6 +382,46 @@ extern "C" int mirec_sweep_wave_build(const int64_t *rowptr, const int32_t *col,
   return MIREC_OK;
 }
 
+// The 4-byte form of the slots above: the local row in the top row_bits bits
+// (all ones = the padding row -1), the column relative to src0 below them.
+extern "C" int mirec_sweep_wave_pack(const int64_t *slot8, int64_t n_slots, int64_t src0,
+                                     int64_t n_src, int32_t tile_rows, uint32_t *slot4,
+                                     int32_t *row_bits) {
+  if (slot8 == nullptr || slot4 == nullptr || row_bits == nullptr || n_slots < 0 || src0 < 0 ||
+      n_src < 0 || tile_rows <= 0)
+    return MIREC_ERR_ARG;
+  int bits = 1;
+  while (bits < 31 && ((int64_t)1 << bits) <= (int64_t)tile_rows) ++bits;
+  if (((int64_t)1 << bits) <= (int64_t)tile_rows) return MIREC_ERR_RANGE;
+  const int col_bits = 32 - bits;
+  if (n_src > ((int64_t)1 << col_bits)) return MIREC_ERR_RANGE;
+  const uint32_t pad_row = (1u << bits) - 1u;
+  const int n_thr = (int)std::max<int64_t>(
+      1, std::min<int64_t>(16, std::min<int64_t>((int64_t)std::thread::hardware_concurrency(),
+                                                 n_slots / (1 << 20) + 1)));
+  std::vector<int> bad(n_thr, 0);
+  auto work = [&](int th) {
+    const int64_t i0 = n_slots * th / n_thr, i1 = n_slots * (th + 1) / n_thr;
+    for (int64_t i = i0; i < i1; ++i) {
+      const int64_t c = (int64_t)(uint32_t)((uint64_t)slot8[i] & 0xffffffffull) - src0;
+      const int32_t r = (int32_t)(slot8[i] >> 32);
+      if (c < 0 || c >= n_src || r < -1 || r >= tile_rows) {
+        bad[th] = 1;
+        return;
+      }
+      slot4[i] = ((r < 0 ? pad_row : (uint32_t)r) << col_bits) | (uint32_t)c;
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < n_thr; ++t) th.emplace_back(work, t);
+  work(0);
+  for (auto &x : th) x.join();
+  for (int b : bad)
+    if (b) return MIREC_ERR_RANGE;
+  *row_bits = bits;
+  return MIREC_OK;
+}
+
 // Per-user positive CDF for the weighted samplers (the sample_pow option,
 // negative_sample.py:53-56): probs[e - rowptr[0]] = the probability of entry
 // e of its user row (rows 0 .. n_users - 1, the allPos order), each row's

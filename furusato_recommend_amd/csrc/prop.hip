@@ -55,6 +55,11 @@
 // Epilogue (per row, LPR lanes): z = dinv_i * sum + seed[slot_i];
 // xs_out = dinv_i * z (next layer's pre-scaled input);
 // o = (z + addend)/divisor + seed2[slot_i]; out = o or Adam(param; grad=o).
+#include <mutex>
+#include <set>
+#include <type_traits>
+#include <utility>
+
 #include "common.h"
 
 namespace mirec {
@@ -122,6 +127,9 @@ constexpr int kScaled = 8;
 // ... and with this bit every entry is kept or dropped by edge_keep (edge
 // dropout; never together with kWeighted or kScaled: refused by the host).
 constexpr int kDropout = 16;
+// ... and with this bit fused Adam streams its table and moments
+// (row_epilogue's STREAM; full unmasked PRESCALED launches at d = 64 only).
+constexpr int kStream = 32;
 
 __device__ __forceinline__ bool bit_set(const uint8_t *bm, int64_t i) { return bm[i] != 0; }
 
@@ -245,9 +253,24 @@ __device__ __forceinline__ float4 combine_groups(float4 s) {
   return s;
 }
 
+// Non-temporal forms of ld4 / st4, for streams touched once per step.
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld4_nt(const float *p) {
+  const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t *>(p));
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void st4_nt(float *p, float4 v) {
+  const f32x4_t t = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(t, reinterpret_cast<f32x4_t *>(p));
+}
+
 // SCALED: a.dinv is the row sum's scale (set so by the host) and the row
 // written to xs_out is scaled by scale_next instead.
-template <int D, bool SCALED = false>
+// STREAM (mirec_prop_t.adam_stream): fused Adam reads and writes the table
+// and its two moments non-temporally: 6 streams touched once per step, which
+// otherwise pass through the caches that hold the gathered rows.  xs_out (the
+// next step's gathered input), out, addend and the seed rows stay as they are.
+template <int D, bool SCALED = false, bool STREAM = false>
 __device__ __forceinline__ void row_epilogue(const PropK &a, int64_t row, float4 s, int sub) {
   const float di = a.dinv[row];
   float dn = di;
@@ -265,7 +288,12 @@ __device__ __forceinline__ void row_epilogue(const PropK &a, int64_t row, float4
   if (a.divisor != 1.f) o = f4_div(o, a.divisor);
   if (a.seed2 != nullptr && sl >= 0) o = f4_add(o, ld4(a.seed2 + (int64_t)sl * D + sub * 4));
   if (a.param != nullptr) {
-    float4 p = ld4(a.param + off), m = ld4(a.m + off), v = ld4(a.v + off);
+    float4 p, m, v;
+    if constexpr (STREAM) {
+      p = ld4_nt(a.param + off), m = ld4_nt(a.m + off), v = ld4_nt(a.v + off);
+    } else {
+      p = ld4(a.param + off), m = ld4(a.m + off), v = ld4(a.v + off);
+    }
     // torch.optim.Adam single-tensor path (torch/optim/adam.py:457-547):
     // exp_avg.lerp_(g, 1-b1); exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2);
     // denom = sqrt(v)/sqrt(bc2) + eps; p.addcdiv_(m, denom, -lr/bc1) — the
@@ -274,9 +302,15 @@ __device__ __forceinline__ void row_epilogue(const PropK &a, int64_t row, float4
     adam1(p.y, m.y, v.y, o.y, a.adam);
     adam1(p.z, m.z, v.z, o.z, a.adam);
     adam1(p.w, m.w, v.w, o.w, a.adam);
-    st4(a.param + off, p);
-    st4(a.m + off, m);
-    st4(a.v + off, v);
+    if constexpr (STREAM) {
+      st4_nt(a.param + off, p);
+      st4_nt(a.m + off, m);
+      st4_nt(a.v + off, v);
+    } else {
+      st4(a.param + off, p);
+      st4(a.m + off, m);
+      st4(a.v + off, v);
+    }
     if (a.out != nullptr) st4(a.out + off, o);
     // with Adam, xs_out receives the pre-scaled UPDATED parameter
     if (a.xs_out != nullptr) st4(a.xs_out + off, f4_scale(dn, p));
@@ -298,7 +332,7 @@ constexpr int kWavesPerBlock = 4;
 // MASKED = in_mask filter on neighbours, ROWMASK = row_mask filter on rows
 // (separate instantiations so profiles tell full and pruned launches apart).
 template <int D, int UNROLL, int MODE, bool MASKED, bool ROWMASK, bool WEIGHTED, bool SCALED,
-          bool DROPOUT>
+          bool DROPOUT, bool STREAM = false>
 __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nrows,
                                           int64_t row_waves) {
   constexpr int LPR = D / 4;
@@ -326,7 +360,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
     if (G > 1 && __ballot(deg > a.narrow_max) == 0ull) {
       float4 s = gather<D, NARROW_UNROLL, MODE, MASKED, WEIGHTED, true, SCALED, DROPOUT>(
           a, beg, end, lane, row);
-      if (have) row_epilogue<D, SCALED>(a, row, s, sub);
+      if (have) row_epilogue<D, SCALED, STREAM>(a, row, s, sub);
       return;
     }
 #pragma unroll 1
@@ -339,7 +373,7 @@ __device__ __forceinline__ void prop_work(const PropK &a, int64_t w, int64_t nro
       float4 s =
           gather<D, UNROLL, MODE, MASKED, WEIGHTED, false, SCALED, DROPOUT>(a, rb, re, lane, r);
       s = combine_groups<D>(s);
-      if (lane < LPR) row_epilogue<D, SCALED>(a, r, s, sub);
+      if (lane < LPR) row_epilogue<D, SCALED, STREAM>(a, r, s, sub);
     }
   } else {
     const int64_t sg = w - row_waves;
@@ -415,11 +449,12 @@ MIREC_NO_PK_F32 void prop_kernel(PropK a) {
   constexpr bool WEIGHTED = (MODE_W & kWeighted) != 0;
   constexpr bool SCALED = (MODE_W & kScaled) != 0;
   constexpr bool DROPOUT = (MODE_W & kDropout) != 0;
+  constexpr bool STREAM = (MODE_W & kStream) != 0;
   constexpr int G = 64 / (D / 4);
   // wave index made provably uniform (SGPR): loop control stays scalar
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (!ROWMASK || a.row_list == nullptr) {
-    prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED, SCALED, DROPOUT>(
+    prop_work<D, UNROLL, MODE, MASKED, ROWMASK, WEIGHTED, SCALED, DROPOUT, STREAM>(
         a, (int64_t)blockIdx.x * kWavesPerBlock + wid, a.n_rows, a.row_waves);
     return;
   }
@@ -728,7 +763,10 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void prop_finalize(PropK a, co
 // they drift tens of bands apart: the per-wave form below has an optional
 // per-XCD pacing for that).
 constexpr int kSweepThreads = 512;
-constexpr int kSweepLdsMax = 64 * 1024;
+// (80 KB: two workgroups fill a CU's 160 KB; the group form's tiles stay
+// within the 64 KB a launch gets without asking)
+constexpr int kSweepLdsMax = 80 * 1024;
+constexpr int kSweepLdsDefault = 64 * 1024;  // dynamic LDS of a launch that asks for no more
 
 struct SweepK {
   const int64_t *gptr;
@@ -876,7 +914,7 @@ MIREC_NO_PK_F32 void prop_sweep_kernel(PropK a, SweepK s) {
 // workgroups and nothing depends on which of them are resident.
 struct SweepWaveK {
   const int64_t *wptr;
-  const long long *slot;  // (lrow << 32) | col per slot; lrow -1 = padding
+  const long long *slot;  // (lrow << 32) | col per slot; lrow -1 = padding (PACKED: below)
   int64_t n_slots;
   int64_t row0;
   int64_t n_rows;
@@ -886,8 +924,15 @@ struct SweepWaveK {
   int32_t n_tiles;
   int32_t band_rows;
   int32_t n_bands;
+  int32_t row_bits;  // PACKED: the row field's width (in the struct's tail padding)
 };
 
+// PACKED (mirec_sweep_wave_pack): `slot` holds 4-byte slots, the local row in
+// the top row_bits bits (all ones = padding), the column relative to src0
+// below them: one 256-B load per 64-slot chunk.  A chunk is decoded once into
+// the same (absolute column, local row or -1) pair per lane; everything after
+// that is the 8-byte form's code.
+//
 // Two optional instantiations beside the production one (AUX = kAuxNone,
 // whose code they leave as it is):
 //
@@ -934,7 +979,8 @@ __device__ __forceinline__ unsigned pace_read(const unsigned *p) {
   return v;
 }
 
-template <int D, int U, bool SCALED, int AUX = kAuxNone>
+template <int D, int U, bool SCALED, int AUX = kAuxNone, bool PACKED = false,
+          bool STREAM = false>
 __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK &s,
                                                 const SweepAuxK &x = SweepAuxK{}) {
   constexpr int LPR = D / 4;
@@ -947,7 +993,10 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
   const int sub = lane % LPR;
   const int g = lane / LPR;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long long kPadRow = (long long)0xffffffff00000000ull;
+  using Slot = typename std::conditional<PACKED, unsigned, long long>::type;
+  const Slot *slots = reinterpret_cast<const Slot *>(s.slot);
+  [[maybe_unused]] const int col_bits = 32 - s.row_bits;
+  const Slot kPadRow = PACKED ? (Slot)(~0u << col_bits) : (Slot)0xffffffff00000000ull;
   const int64_t last = s.n_slots - 1;  // >= 0 (checked by the host)
   // kAuxPace (wave 0): band advances of this workgroup since the kernel's
   // start, how many of them the XCD's sum holds, advances until the next poll
@@ -1002,7 +1051,7 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
     const int n_batches = __builtin_amdgcn_readfirstlane((int)((end - pos) / (U * G)));
     // slots past the stream's end are padding (their column: a slot of the
     // layout, inside the source block)
-    long long cur = __builtin_nontemporal_load(s.slot + min(pos + lane, last));
+    Slot cur = __builtin_nontemporal_load(slots + min(pos + lane, last));
     if (lane >= n_batches * (U * G)) cur |= kPadRow;
     int band = 0;
     int64_t hi = s.src0 + s.band_rows;
@@ -1015,10 +1064,16 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
     }
 #pragma unroll 1
     for (int b0 = 0; b0 < n_batches; b0 += NB) {
-      long long nxt = __builtin_nontemporal_load(s.slot + min(pos + 64 + lane, last));
+      Slot nxt = __builtin_nontemporal_load(slots + min(pos + 64 + lane, last));
       if (b0 * (U * G) + 64 + lane >= n_batches * (U * G)) nxt |= kPadRow;
-      const int ccol = (int)(cur & 0xffffffffll);
-      const int crow = (int)(cur >> 32);
+      int ccol, crow;
+      if constexpr (PACKED) {
+        ccol = (int)s.src0 + (int)(cur & ~kPadRow);
+        crow = cur >= kPadRow ? -1 : (int)(cur >> col_bits);
+      } else {
+        ccol = (int)(cur & 0xffffffffll);
+        crow = (int)(cur >> 32);
+      }
 #pragma unroll
       for (int k = 0; k < NB; ++k) {
         // the wave enters the next band once its oldest pending entry lies
@@ -1073,7 +1128,8 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
     }
     // rows are private to their wave
     for (int lr = lr0 + g; lr < lr1; lr += G)
-      row_epilogue<D, SCALED>(a, s.row0 + tile_row0 + lr, sweep_acc[lr * LPR + sub], sub);
+      row_epilogue<D, SCALED, STREAM>(a, s.row0 + tile_row0 + lr, sweep_acc[lr * LPR + sub],
+                                      sub);
     if constexpr (AUX == kAuxStamp) {
       stamp(s.n_bands);
       if (wid == 0) {  // (a wave's LDS instructions complete in order)
@@ -1107,16 +1163,16 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
   }
 }
 
-template <int D, int U, bool SCALED>
+template <int D, int U, bool SCALED, bool PACKED = false, bool STREAM = false>
 __global__ __launch_bounds__(kSweepThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 MIREC_NO_PK_F32 void prop_sweep_wave_kernel(PropK a, SweepWaveK s) {
-  sweep_wave_work<D, U, SCALED>(a, s);
+  sweep_wave_work<D, U, SCALED, kAuxNone, PACKED, STREAM>(a, s);
 }
 
-template <int D, int U, bool SCALED, int AUX>
+template <int D, int U, bool SCALED, int AUX, bool PACKED = false, bool STREAM = false>
 __global__ __launch_bounds__(kSweepThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 MIREC_NO_PK_F32 void prop_sweep_wave_aux_kernel(PropK a, SweepWaveK s, SweepAuxK x) {
-  sweep_wave_work<D, U, SCALED, AUX>(a, s, x);
+  sweep_wave_work<D, U, SCALED, AUX, PACKED, STREAM>(a, s, x);
 }
 
 using PropFn = void (*)(PropK);
@@ -1169,7 +1225,7 @@ static PropFn prop_kernel_for(int mode, bool masked, bool rowmask, bool weighted
 
 template <int D, int UNROLL>
 static int launch_prop(const mirec_csr_t *c, PropK k, int64_t list_cap, int mode,
-                       hipStream_t st, bool dropout = false) {
+                       hipStream_t st, bool dropout = false, bool stream = false) {
   constexpr int G = 64 / (D / 4);
   const int64_t rows = k.row_list != nullptr ? list_cap : c->n_rows;
   k.row_waves = (rows + G - 1) / G;
@@ -1181,9 +1237,18 @@ static int launch_prop(const mirec_csr_t *c, PropK k, int64_t list_cap, int mode
     blocks = std::min(blocks, kListBlocks);
   }
   if (blocks > 0) {
-    const PropFn kernel =
+    PropFn kernel =
         prop_kernel_for<D, UNROLL>(mode, k.in_mask != nullptr, k.row_mask != nullptr,
                                    !dropout && k.val != nullptr, scaled, dropout);
+    if constexpr (D == 64) {
+      // a full launch with streaming Adam (the other shapes have no such form:
+      // the flag is a cache hint)
+      if (stream && k.param != nullptr && mode == MIREC_IN_PRESCALED && k.in_mask == nullptr &&
+          k.row_mask == nullptr && k.val == nullptr && !dropout)
+        kernel = scaled
+                     ? prop_kernel<D, UNROLL, MIREC_IN_PRESCALED | kScaled | kStream, false, false>
+                     : prop_kernel<D, UNROLL, MIREC_IN_PRESCALED | kStream, false, false>;
+    }
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, k);
     MIREC_LAUNCH_CHECK();
   }
@@ -1347,7 +1412,7 @@ static bool sweep_qualifies(const mirec_csr_t *c, const mirec_prop_t *p, const m
   if (sw->groups <= 0 || sw->groups > kSweepThreads / (64 / 4)) return false;
   if ((int64_t)sw->groups * sw->group_rows < sw->tile_rows) return false;
   if ((int64_t)sw->n_tiles * sw->tile_rows < sw->n_rows) return false;
-  if ((int64_t)sw->tile_rows * 64 * 4 > kSweepLdsMax) return false;
+  if ((int64_t)sw->tile_rows * 64 * 4 > kSweepLdsDefault) return false;
   return true;
 }
 
@@ -1395,7 +1460,28 @@ static bool sweep_wave_valid(const mirec_csr_t *c, const mirec_sweep_wave_t *w, 
   if ((int64_t)w->n_tiles * w->tile_rows < n_rows) return false;
   if ((int64_t)(w->n_tiles - 1) * w->tile_rows >= n_rows) return false;
   if ((int64_t)w->tile_rows * 64 * 4 > kSweepLdsMax) return false;
+  if (w->row_bits != 0) {  // packed slots: both fields hold what the layout names
+    if (w->row_bits < 1 || w->row_bits > 31) return false;
+    if ((int64_t)w->tile_rows >= ((int64_t)1 << w->row_bits)) return false;
+    if (w->n_src > ((int64_t)1 << (32 - w->row_bits))) return false;
+  }
   return w->grid > 0 && w->grid <= w->n_tiles;
+}
+
+// A launch with more dynamic LDS than the default limit needs the kernel's
+// limit raised first: once per kernel and device.
+static int sweep_lds_allow(const void *kernel, size_t lds) {
+  if (lds <= (size_t)kSweepLdsDefault) return MIREC_OK;
+  static std::mutex mu;
+  static std::set<std::pair<const void *, int>> raised;
+  int dev = 0;
+  MIREC_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  if (raised.count({kernel, dev}) != 0) return MIREC_OK;
+  MIREC_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kSweepLdsMax));
+  raised.insert({kernel, dev});
+  return MIREC_OK;
 }
 
 // The stamping launch's buffers (mirec_sweep_wave_stamp).
@@ -1415,7 +1501,7 @@ static int32_t sweep_wave_bands(const mirec_sweep_wave_t *w) {
 template <int D>
 static int launch_sweep_wave(const PropK &k, const mirec_sweep_wave_t *w, hipStream_t st,
                              const mirec_sweep_pace_t *pace = nullptr, int block = 0,
-                             const SweepStamp *stamp = nullptr) {
+                             const SweepStamp *stamp = nullptr, bool stream = false) {
   SweepWaveK s;
   s.wptr = w->wptr;
   s.slot = reinterpret_cast<const long long *>(w->slot);
@@ -1428,16 +1514,21 @@ static int launch_sweep_wave(const PropK &k, const mirec_sweep_wave_t *w, hipStr
   s.n_tiles = w->n_tiles;
   s.band_rows = w->band_rows;
   s.n_bands = sweep_wave_bands(w);
+  s.row_bits = w->row_bits;
   size_t lds = (size_t)w->tile_rows * D * sizeof(float);
   const bool scaled = k.scale_next != nullptr;
+  const bool packed = w->row_bits != 0;
+  // streaming Adam has packed forms only (a cache hint: 8-byte layouts run without it)
+  stream = stream && packed && k.param != nullptr;
   if (stamp != nullptr) {
     SweepAuxK x = {};
     x.stamps = reinterpret_cast<long long *>(stamp->stamps);
     x.meta = stamp->meta;
     lds += (size_t)(s.n_bands + 1) * sizeof(long long);
+    if (packed) return MIREC_ERR_ARG;  // the stamping kernel reads 8-byte slots
     const auto kernel = scaled ? prop_sweep_wave_aux_kernel<D, 4, true, kAuxStamp>
                                : prop_sweep_wave_aux_kernel<D, 4, false, kAuxStamp>;
-    if (lds > (size_t)kSweepLdsMax &&
+    if (lds > (size_t)kSweepLdsDefault &&
         hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return MIREC_ERR_HIP;
@@ -1448,12 +1539,27 @@ static int launch_sweep_wave(const PropK &k, const mirec_sweep_wave_t *w, hipStr
     x.lead = pace->lead_bands[block];
     x.every = pace->every[block];
     x.nap = pace->nap[block];
-    const auto kernel = scaled ? prop_sweep_wave_aux_kernel<D, 4, true, kAuxPace>
-                               : prop_sweep_wave_aux_kernel<D, 4, false, kAuxPace>;
+    auto kernel = scaled ? prop_sweep_wave_aux_kernel<D, 4, true, kAuxPace>
+                         : prop_sweep_wave_aux_kernel<D, 4, false, kAuxPace>;
+    if (packed)
+      kernel = scaled ? prop_sweep_wave_aux_kernel<D, 4, true, kAuxPace, true>
+                      : prop_sweep_wave_aux_kernel<D, 4, false, kAuxPace, true>;
+    if (stream)
+      kernel = scaled ? prop_sweep_wave_aux_kernel<D, 4, true, kAuxPace, true, true>
+                      : prop_sweep_wave_aux_kernel<D, 4, false, kAuxPace, true, true>;
+    const int rc = sweep_lds_allow(reinterpret_cast<const void *>(kernel), lds);
+    if (rc != MIREC_OK) return rc;
     hipLaunchKernelGGL(kernel, dim3((unsigned)w->grid), dim3(kSweepThreads), lds, st, k, s, x);
   } else {
-    const auto kernel = scaled ? prop_sweep_wave_kernel<D, 4, true>
-                               : prop_sweep_wave_kernel<D, 4, false>;
+    auto kernel = scaled ? prop_sweep_wave_kernel<D, 4, true> : prop_sweep_wave_kernel<D, 4, false>;
+    if (packed)
+      kernel = scaled ? prop_sweep_wave_kernel<D, 4, true, true>
+                      : prop_sweep_wave_kernel<D, 4, false, true>;
+    if (stream)
+      kernel = scaled ? prop_sweep_wave_kernel<D, 4, true, true, true>
+                      : prop_sweep_wave_kernel<D, 4, false, true, true>;
+    const int rc = sweep_lds_allow(reinterpret_cast<const void *>(kernel), lds);
+    if (rc != MIREC_OK) return rc;
     hipLaunchKernelGGL(kernel, dim3((unsigned)w->grid), dim3(kSweepThreads), lds, st, k, s);
   }
   MIREC_LAUNCH_CHECK();
@@ -1563,6 +1669,7 @@ static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sw
   }
   const int64_t cap = p->row_list_cap;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool nt = p->adam_stream != 0 && p->param != nullptr;
   if (stamp != nullptr) {
     // the measurement: one block's launch, nothing else (its other rows stay unwritten)
     const mirec_sweep_wave_t *w = stamp->layout;
@@ -1576,9 +1683,10 @@ static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sw
   if (sweep_qualifies(c, p, sw)) return launch_sweep<64, 4>(c, k, sw, st);
   if (wi != nullptr && sweep_launch_qualifies(c, p) &&
       sweep_wave_valid(c, wi, wi->row0, c->n_rows - wi->row0)) {
-    const int rc = launch_sweep_wave<64>(k, wi, st, pace, 0);
+    const int rc = launch_sweep_wave<64>(k, wi, st, pace, 0, nullptr, nt);
     if (rc != MIREC_OK || wi->row0 == 0) return rc;
-    if (sweep_wave_valid(c, wu, 0, wi->row0)) return launch_sweep_wave<64>(k, wu, st, pace, 1);
+    if (sweep_wave_valid(c, wu, 0, wi->row0))
+      return launch_sweep_wave<64>(k, wu, st, pace, 1, nullptr, nt);
     return launch_head<64, 4>(c, k, wi->row0, st);
   }
   if (seeded != nullptr) {  // (a launch of the seeded shape: mirec_propagate_seeded)
@@ -1601,7 +1709,7 @@ static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sw
     case 8: return launch_prop<8, 1>(c, k, cap, p->in_mode, st, dropout);
     case 16: return launch_prop<16, 1>(c, k, cap, p->in_mode, st, dropout);
     case 32: return launch_prop<32, 2>(c, k, cap, p->in_mode, st, dropout);
-    case 64: return launch_prop<64, 4>(c, k, cap, p->in_mode, st, dropout);
+    case 64: return launch_prop<64, 4>(c, k, cap, p->in_mode, st, dropout, nt);
     case 128: return launch_prop<128, 4>(c, k, cap, p->in_mode, st, dropout);
     case 256: return launch_prop<256, 8>(c, k, cap, p->in_mode, st, dropout);
   }

@@ -68,6 +68,8 @@ SWEEP_PACE = {"items": (8, 16, 16), "users": (4, 4, 16)}
 # Defaults of PropagationEngine.seeded_first and seeded_lds_bytes (DESIGN.md
 # §24): 16 KB for both bit arrays keeps 8 workgroups per CU resident.
 SEEDED_FIRST = True
+# Default of PropagationEngine.adam_stream.
+ADAM_STREAM = True
 SEEDED_LDS_BYTES = 16 * 1024
 
 
@@ -375,6 +377,13 @@ class PropagationEngine:
         self._wave_sizes = {"items": (None, None), "users": (None, None), "max_grid": None}
         self.sweep_wave = self.sweep_wave_users = None
         self._sweep_form, self._sweep_users = SWEEP_FORM, SWEEP_USERS
+        # the wave form's slot streams: None = the graph
+        # module's default (4-byte packed slots where the block fits them),
+        # False = 8-byte slots
+        self._sweep_packed = None
+        # fused Adam streams the table and its moments past the caches (full
+        # launches at d = 64; a cache hint, results do not depend on it)
+        self.adam_stream = ADAM_STREAM
         # per-XCD pacing of the wave form's launches: None, or
         # {"items": (lead_bands, every, nap) | None, "users": ... | None}
         self.sweep_pace = SWEEP_PACE
@@ -551,6 +560,7 @@ class PropagationEngine:
         p.wide_list = ptr(wide_list)
         p.wide_count = ptr(wide_count)
         p.narrow_max = int(self.narrow_max)
+        p.adam_stream = int(bool(self.adam_stream))
         ev = self.prop_events
         if ev is not None:
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -618,6 +628,9 @@ class PropagationEngine:
         lay = self.sweep_wave if block == "items" else self.sweep_wave_users
         if lay is None:
             raise RuntimeError(f"no wave-form layout of the {block} block")
+        if lay.desc.row_bits:  # the stamping kernel reads 8-byte slots
+            lay = self.g.sweep_wave_layout(self.dim, block, *self._wave_sizes[block],
+                                           max_grid=self._wave_sizes["max_grid"], packed=False)
         d = lay.desc
         bands = max(1, -(-d.n_src // d.band_rows))
         stamps = torch.zeros(d.n_tiles, bands + 1, dtype=torch.int64, device=self.g.device)
@@ -712,10 +725,34 @@ class PropagationEngine:
         ws = self._wave_sizes
         if self.sweep_wave is None:
             self.sweep_wave = self.g.sweep_wave_layout(self.dim, "items", *ws["items"],
-                                                       max_grid=ws["max_grid"])
+                                                       max_grid=ws["max_grid"],
+                                                       packed=self._sweep_packed)
         if self._sweep_users and self.sweep_wave is not None and self.sweep_wave_users is None:
             self.sweep_wave_users = self.g.sweep_wave_layout(self.dim, "users", *ws["users"],
-                                                             max_grid=ws["max_grid"])
+                                                             max_grid=ws["max_grid"],
+                                                             packed=self._sweep_packed)
+
+    @property
+    def sweep_packed(self):
+        return self._sweep_packed
+
+    @sweep_packed.setter
+    def sweep_packed(self, on):
+        self._sweep_packed = None if on is None else bool(on)
+        self.sweep_wave = self.sweep_wave_users = None
+        self._wave_layouts()
+
+    @property
+    def sweep_user_tile(self):
+        """Rows per tile of the user block's wave-form layout (None: the
+        default of Graph.sweep_wave_layout)."""
+        return self._wave_sizes["users"][0]
+
+    @sweep_user_tile.setter
+    def sweep_user_tile(self, rows):
+        self._wave_sizes["users"] = (rows, self._wave_sizes["users"][1])
+        self.sweep_wave_users = None
+        self._wave_layouts()
 
     @property
     def sweep_form(self) -> str:

@@ -34,9 +34,35 @@ DEFAULT_SPLIT = 2048
 # LDS accumulators are capped at SWEEP_LDS_BYTES, and a user block that fits
 # one XCD's L2 (4 MiB) gains nothing from the sweep.
 SWEEP_BAND_BYTES = 1 << 20
-SWEEP_LDS_BYTES = 64 << 10
+SWEEP_LDS_BYTES = 80 << 10  # the wave form's cap: two workgroups fill a CU's 160 KB
+SWEEP_LDS_DEFAULT_BYTES = 64 << 10  # the group form's cap and the item tiles' default cap
 SWEEP_L2_BYTES = 4 << 20
 SWEEP_WAVES = 8  # MIREC_SWEEP_WAVES: the waves of a sweep workgroup
+# The wave form's default tile of the user block: "even" = the
+# rule of sweep_user_tile_rows under SWEEP_LDS_BYTES, an int = that many rows.
+SWEEP_USER_TILE_ROWS = "even"
+# Default of the wave form's slot streams: 4-byte packed slots where the
+# block fits them (mirec_sweep_wave_pack), else and when False 8-byte slots.
+SWEEP_PACKED = True
+
+
+def sweep_user_tile_rows(n_rows: int, workgroups: int, cap: int) -> int:
+    """Tile of a block swept in passes by ``workgroups`` workgroups.  Every
+    pass fetches the whole source block again, so the passes stay as few as
+    the cap allows; among the tiles with that many passes, the largest t, a
+    whole number of rows per wave, whose ceil(n_rows / t) tiles leave at most
+    1 % of the last pass's workgroups without one (passes * workgroups <=
+    1.01 * tiles).  The cap if no t does."""
+    cap = max(1, int(cap))
+    fewest = -(-(-(-n_rows // cap)) // workgroups)
+    for t in range(cap - cap % SWEEP_WAVES, 0, -SWEEP_WAVES):
+        tiles = -(-n_rows // t)
+        passes = -(-tiles // workgroups)
+        if tiles < workgroups or passes > fewest:
+            break
+        if passes * workgroups * 100 <= 101 * tiles:
+            return t
+    return cap
 
 
 class SweepLayout:
@@ -362,7 +388,7 @@ class Graph:
             return None
         explicit = not (tile_rows is None and group_rows is None and band_rows is None)
         row_bytes = dim * 4
-        max_tile = SWEEP_LDS_BYTES // row_bytes
+        max_tile = SWEEP_LDS_DEFAULT_BYTES // row_bytes
         if not explicit:
             n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
             if mi < n_cu or nu * row_bytes <= SWEEP_L2_BYTES:
@@ -399,25 +425,30 @@ class Graph:
         return lay
 
     def sweep_wave_layout(self, dim: int, block: str = "items", tile_rows: int | None = None,
-                          band_rows: int | None = None, max_grid: int | None = None):
+                          band_rows: int | None = None, max_grid: int | None = None,
+                          packed: bool | None = None):
         """The per-wave form of the column-sweep layout (mirec_sweep_wave_t,
         DESIGN.md §14) of the item rows (``block="items"``, gathering from the
         user block) or of the user rows (``"users"``, gathering from the item
         block), or None when the graph does not qualify: the conditions of
         ``sweep_layout``, and for the user rows with default sizes an item
         block larger than one XCD's L2.  Defaults: for the items two tiles per
-        CU (one pass), for the users tiles of SWEEP_LDS_BYTES swept in passes
-        by two workgroups per CU; bands of SWEEP_BAND_BYTES of source rows.
+        CU (one pass), for the users tiles of SWEEP_USER_TILE_ROWS swept in
+        passes by two workgroups per CU; bands of SWEEP_BAND_BYTES of source rows.
         ``max_grid`` caps the workgroups launched (tests force several passes
-        on a small graph).  Built once per (graph, sizes)."""
-        key = ("wave", dim, block, tile_rows, band_rows, max_grid)
+        on a small graph).  ``packed`` (None: SWEEP_PACKED) uploads the slots
+        in their 4-byte form when the block fits it (``desc.row_bits`` > 0),
+        the 8-byte slots otherwise.  Built once per (graph, sizes, form)."""
+        packed = SWEEP_PACKED if packed is None else bool(packed)
+        key = ("wave", dim, block, tile_rows, band_rows, max_grid, packed)
         cache = self.__dict__.setdefault("_sweeps", {})
         if key in cache:
             return cache[key]
-        cache[key] = lay = self._build_sweep_wave(dim, block, tile_rows, band_rows, max_grid)
+        cache[key] = lay = self._build_sweep_wave(dim, block, tile_rows, band_rows, max_grid,
+                                                  packed)
         return lay
 
-    def _build_sweep_wave(self, dim, block, tile_rows, band_rows, max_grid):
+    def _build_sweep_wave(self, dim, block, tile_rows, band_rows, max_grid, packed):
         nu, mi = self.n_users, self.m_items
         if block not in ("items", "users"):
             raise ValueError(f"block: 'items' or 'users', got {block!r}")
@@ -438,9 +469,13 @@ class Graph:
                 return None
         row0, n_rows, src0, n_src = (nu, mi, 0, nu) if block == "items" else (0, nu, nu, mi)
         if tile_rows is None:
-            tile_rows = max_tile
             if block == "items":
-                tile_rows = min(max_tile, max(1, -(-mi // (2 * n_cu))))
+                tile_rows = min(SWEEP_LDS_DEFAULT_BYTES // row_bytes,
+                                max(1, -(-mi // (2 * n_cu))))
+            elif SWEEP_USER_TILE_ROWS == "even":
+                tile_rows = sweep_user_tile_rows(nu, 2 * n_cu, max_tile)
+            else:
+                tile_rows = int(SWEEP_USER_TILE_ROWS)
         if band_rows is None:
             band_rows = max(1, SWEEP_BAND_BYTES // row_bytes)
         tile_rows, band_rows = int(tile_rows), int(band_rows)
@@ -470,11 +505,21 @@ class Graph:
         lay = SweepWaveLayout()
         lay.n_entries = n_ent
         lay.wptr = torch.from_numpy(wptr).to(self.device)
-        lay.slot = torch.from_numpy(slot[:n_slots.value]).to(self.device)
+        slot, row_bits = slot[:n_slots.value], ctypes.c_int32(0)
+        if packed:
+            slot4 = np.empty(n_slots.value, np.uint32)
+            rc = lib.mirec_sweep_wave_pack(slot.ctypes.data, n_slots.value, src0, n_src,
+                                           tile_rows, slot4.ctypes.data, ctypes.byref(row_bits))
+            if rc == _lib.ERR_RANGE:  # the block does not fit 32 bits: 8-byte slots
+                row_bits.value = 0
+            else:
+                check(rc, "sweep_wave_pack")
+                slot = slot4.view(np.int32)
+        lay.slot = torch.from_numpy(slot).to(self.device)
         lay.desc = SweepWave(row0=row0, n_rows=n_rows, src0=src0, n_src=n_src,
                              n_slots=n_slots.value, tile_rows=tile_rows,
                              wave_rows=-(-tile_rows // SWEEP_WAVES), n_tiles=n_tiles,
-                             band_rows=band_rows, grid=grid, _pad=0,
+                             band_rows=band_rows, grid=grid, row_bits=row_bits.value,
                              wptr=lay.wptr.data_ptr(), slot=lay.slot.data_ptr())
         return lay
 

@@ -232,7 +232,10 @@ typedef struct mirec_prop {
   int32_t narrow_max;       /* rows of degree <= narrow_max are gathered one
                                per lane group (latency-bound short rows);
                                longer ones one per wave.  0 = always wave */
-  int32_t _pad2;
+  int32_t adam_stream;      /* != 0: fused Adam reads and writes param and its
+                               moments non-temporally (streams touched once a
+                               step), where the launch's kernel has such a
+                               form; results do not depend on it */
   const int32_t *wide_list; /* optional second list (with row_list): rows
                                wide_list[0 .. *wide_count) are gathered by a
                                whole 256-thread workgroup each (4 waves split
@@ -410,9 +413,11 @@ typedef struct mirec_sweep_wave {
   int32_t n_tiles;
   int32_t band_rows;
   int32_t grid; /* workgroups launched, 1 .. n_tiles */
-  int32_t _pad;
+  int32_t row_bits; /* 0: `slot` holds the 8-byte slots above; > 0: the 4-byte
+                       packed slots of mirec_sweep_wave_pack with this width
+                       of the row field */
   const int64_t *wptr; /* [n_tiles * MIREC_SWEEP_WAVES + 1], in slots */
-  const int64_t *slot; /* [n_slots] */
+  const int64_t *slot; /* [n_slots] 8-byte, or [n_slots] 4-byte (row_bits > 0) */
 } mirec_sweep_wave_t;
 
 size_t mirec_sweep_wave_sizeof(void);
@@ -427,6 +432,18 @@ int mirec_sweep_wave_build(const int64_t *rowptr, const int32_t *col, int64_t ro
                            int64_t n_rows, int64_t src0, int64_t n_src,
                            int32_t tile_rows, int64_t *wptr, int64_t *slot,
                            int64_t slot_cap, int64_t *n_slots);
+
+/* Host: the 4-byte packed form of the slots mirec_sweep_wave_build wrote (or
+ * of any run of them).  *row_bits = the smallest number of bits b with
+ * tile_rows < 2^b; slot4[i] = (local row field << (32 - b)) | (column - src0),
+ * the all-ones row field standing for the padding row -1.  Half the bytes of
+ * the slot stream; the kernel decodes the same (local row, column) pairs, so
+ * a launch computes bit for bit what it computes from the 8-byte slots.
+ * MIREC_ERR_RANGE, before any array is touched, if the source block does not
+ * fit the column field (n_src > 2^(32 - b)), and if a slot's column lies
+ * outside [src0, src0 + n_src) or its row outside -1 .. tile_rows - 1. */
+int mirec_sweep_wave_pack(const int64_t *slot8, int64_t n_slots, int64_t src0, int64_t n_src,
+                          int32_t tile_rows, uint32_t *slot4, int32_t *row_bits);
 
 /* mirec_propagate_sweep with the per-wave layout `items` (the tail rows of
  * the CSR, as `sw` there).  The rows [0, items->row0) go through the row

@@ -5,6 +5,8 @@ LightGCN d = 64 on the bench.py C2 graph in the forms of the column sweep:
   group        item rows by the group form of the sweep
   wave         item rows by the wave form (§14), user rows by the row kernel
   wave+users   both blocks by the wave form
+  wave+users8  the same with 8-byte slot streams (sweep_packed off, §26; not
+               in the default --forms)
 
 and, with --sizes, the wave form at other (tile_rows, band_rows); with --pace,
 both blocks swept and one of them paced per XCD.  The forms
@@ -48,7 +50,8 @@ def main():
     D = 64
     forms = {"row": {"use_sweep": False}, "group": {"sweep_form": "group"},
              "wave": {"sweep_form": "wave", "sweep_users": False},
-             "wave+users": {"sweep_form": "wave", "sweep_users": True}}
+             "wave+users": {"sweep_form": "wave", "sweep_users": True},
+             "wave+users8": {"sweep_form": "wave", "sweep_users": True, "sweep_packed": False}}
     engines = {}
     for name, sw in forms.items():
         if name not in args.forms.split(","):

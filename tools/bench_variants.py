@@ -40,6 +40,13 @@ VARIANTS = {
     # 
     "seeded_first_off": {"seeded_first": False},
     "seeded_first_on": {"seeded_first": True},
+    # the full launches' three stages of DESIGN.md §26, each on top of the one
+    # before: 8-byte slots / 256-row user tiles / plain Adam is the form before
+    "full_before": {"sweep_packed": False, "sweep_user_tile": 256, "adam_stream": False},
+    "full_packed": {"sweep_packed": True, "sweep_user_tile": 256, "adam_stream": False},
+    "full_tile280": {"sweep_packed": True, "sweep_user_tile": 280, "adam_stream": False},
+    "full_tile320": {"sweep_packed": True, "sweep_user_tile": 320, "adam_stream": False},
+    "full_stream": {"sweep_packed": True, "sweep_user_tile": 280, "adam_stream": True},
 }
 
 
