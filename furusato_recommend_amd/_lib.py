@@ -161,6 +161,9 @@ SIGNATURES = {
     "mirec_propagate_sweep_wave_paced": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(SweepWave),
                                                  POINTER(SweepWave), POINTER(SweepPace),
                                                  c_void_p]),
+    "mirec_propagate_sweep_wave_masked": (c_int, [POINTER(CSR), POINTER(Prop),
+                                                  POINTER(SweepWave), POINTER(SweepWave),
+                                                  POINTER(SweepPace), c_int32, c_void_p]),
     "mirec_sweep_wave_stamp": (c_int, [POINTER(CSR), POINTER(Prop), POINTER(SweepWave), c_void_p,
                                        c_int64, c_void_p, c_void_p]),
     "mirec_drop_sizeof": (c_size_t, []),

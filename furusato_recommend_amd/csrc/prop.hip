@@ -979,8 +979,27 @@ __device__ __forceinline__ unsigned pace_read(const unsigned *p) {
   return v;
 }
 
+//
+// INMASK (mirec_propagate_sweep_wave_masked; unscaled, no STREAM):
+// the sweep of a launch with an in_mask.  Each lane tests the column of its
+// slot against the byte map; a failing lane turns its slot into padding
+// (local row -1: the term is dropped by the pr[u] >= 0 test below) and names
+// the block's first source row src0 as its LOAD column, a valid row that
+// stays in L1 and whose contents are never added.  The byte of chunk i + 1 is
+// loaded in the middle of chunk i, once its slot has arrived (the add of
+// batch 0 has waited for it already) and two batches before it is used: no
+// row load waits for a byte requested in its own iteration.  Every row load
+// stays unconditional and unclamped.
+// The band decision reads the STATIC column of a batch's first slot, before
+// any redirection, so the bands a wave walks, the number of s_barrier it
+// executes per tile (n_bands - 1) and its calls of pace() are those of the
+// unmasked launch of the same layout whatever the mask holds: no wave can
+// miss a barrier that the others of its workgroup execute.  There is no
+// other wait, flag or dependence between workgroups.  A row's passing terms
+// are added in stream order: the sum is bitwise the unmasked sweep's of an
+// input whose masked-out rows are +0.0.
 template <int D, int U, bool SCALED, int AUX = kAuxNone, bool PACKED = false,
-          bool STREAM = false>
+          bool STREAM = false, bool INMASK = false>
 __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK &s,
                                                 const SweepAuxK &x = SweepAuxK{}) {
   constexpr int LPR = D / 4;
@@ -988,6 +1007,8 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
   constexpr int NB = 64 / (U * G);     // batches per 64-slot chunk
   static_assert(G == 4 && U * G == MIREC_SWEEP_BATCH && kSweepThreads / 64 == MIREC_SWEEP_WAVES,
                 "the host layout's steps, batches and waves");
+  static_assert(!INMASK || (!SCALED && !STREAM && AUX != kAuxStamp && NB >= 3),
+                "the masked forms a step uses");
   extern __shared__ float4 sweep_acc[];  // [tile_rows][LPR]
   const int lane = threadIdx.x & 63;
   const int sub = lane % LPR;
@@ -998,6 +1019,11 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
   [[maybe_unused]] const int col_bits = 32 - s.row_bits;
   const Slot kPadRow = PACKED ? (Slot)(~0u << col_bits) : (Slot)0xffffffff00000000ull;
   const int64_t last = s.n_slots - 1;  // >= 0 (checked by the host)
+  // a slot's absolute column (INMASK: the byte map's index)
+  [[maybe_unused]] auto slot_col = [&](Slot v) -> int64_t {
+    if constexpr (PACKED) return s.src0 + (int64_t)(v & ~kPadRow);
+    return (int64_t)(v & 0xffffffffll);
+  };
   // kAuxPace (wave 0): band advances of this workgroup since the kernel's
   // start, how many of them the XCD's sum holds, advances until the next poll
   int adv = 0, told = 0, due = 0;
@@ -1053,6 +1079,16 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
     // layout, inside the source block)
     Slot cur = __builtin_nontemporal_load(slots + min(pos + lane, last));
     if (lane >= n_batches * (U * G)) cur |= kPadRow;
+    // INMASK: the byte of this lane's slot of `cur` (every slot's column lies
+    // inside the source block, padding and slots past the end included)
+    [[maybe_unused]] int cmask = 1, nmask = 1;
+    if constexpr (INMASK) {
+      cmask = a.in_mask[slot_col(cur)];
+      // (the byte's wait stands here, before the loop, and the next chunk's
+      // at the loop's end: at the loop's head no byte is pending on either
+      // path, so the compiler puts no wait for one before the row loads)
+      asm volatile("" : "+v"(cmask));
+    }
     int band = 0;
     int64_t hi = s.src0 + s.band_rows;
     float4 pv[U];
@@ -1074,6 +1110,15 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
         ccol = (int)(cur & 0xffffffffll);
         crow = (int)(cur >> 32);
       }
+      // the column a lane's row load names: its own, or src0 when masked out
+      // (ccol itself keeps deciding the bands)
+      int lcol = ccol;
+      if constexpr (INMASK) {
+        if (cmask == 0) {
+          crow = -1;
+          lcol = (int)s.src0;
+        }
+      }
 #pragma unroll
       for (int k = 0; k < NB; ++k) {
         // the wave enters the next band once its oldest pending entry lies
@@ -1086,12 +1131,16 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
           hi += s.band_rows;
           stamp(band);
         }
+        if constexpr (INMASK) {
+          // the next chunk's bytes: its slots arrived before batch 0 was added
+          if (k == 2) nmask = a.in_mask[slot_col(nxt)];
+        }
         float4 v[U];
         int r[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int src = k * U * G + u * G + g;
-          const int j = __shfl(ccol, src);
+          const int j = __shfl(lcol, src);
           r[u] = __shfl(crow, src);
           v[u] = ld4(a.x_in + (int64_t)j * D + sub * 4);
         }
@@ -1112,6 +1161,12 @@ __device__ __forceinline__ void sweep_wave_work(const PropK &a, const SweepWaveK
       }
       pos += 64;
       cur = nxt;
+      if constexpr (INMASK) {
+        // a counted wait: the two batches of row loads issued after the byte
+        // stay in flight
+        asm volatile("" : "+v"(nmask));
+        cmask = nmask;
+      }
     }
     while (band + 1 < s.n_bands) {  // every wave executes the same number of barriers
       pace();
@@ -1173,6 +1228,20 @@ template <int D, int U, bool SCALED, int AUX, bool PACKED = false, bool STREAM =
 __global__ __launch_bounds__(kSweepThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 MIREC_NO_PK_F32 void prop_sweep_wave_aux_kernel(PropK a, SweepWaveK s, SweepAuxK x) {
   sweep_wave_work<D, U, SCALED, AUX, PACKED, STREAM>(a, s, x);
+}
+
+// The in_mask forms (sweep_wave_work's INMASK): kernels of their own, so the
+// ones above keep their names and their code.
+template <int D, int U, bool PACKED>
+__global__ __launch_bounds__(kSweepThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+MIREC_NO_PK_F32 void prop_sweep_wave_masked_kernel(PropK a, SweepWaveK s) {
+  sweep_wave_work<D, U, false, kAuxNone, PACKED, false, true>(a, s);
+}
+
+template <int D, int U, int AUX, bool PACKED>
+__global__ __launch_bounds__(kSweepThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+MIREC_NO_PK_F32 void prop_sweep_wave_masked_aux_kernel(PropK a, SweepWaveK s, SweepAuxK x) {
+  sweep_wave_work<D, U, false, AUX, PACKED, false, true>(a, s, x);
 }
 
 using PropFn = void (*)(PropK);
@@ -1395,11 +1464,15 @@ static int launch_edge_dot(const mirec_csr_t *c, const float *a, const float *b,
 // The sweep path's qualifying rule; the graph-side part
 // (bipartite, enough rows, a source block larger than L2) is decided where
 // the layout is built.  First the launch-side part, shared by both forms.
-static bool sweep_launch_qualifies(const mirec_csr_t *c, const mirec_prop_t *p) {
+// `in_mask_ok`: the caller has a masked form for the launch (the wave form
+// only, and only where mirec_propagate_sweep_wave_masked asks for it).
+static bool sweep_launch_qualifies(const mirec_csr_t *c, const mirec_prop_t *p,
+                                   bool in_mask_ok = false) {
   if (p->dim != 64) return false;
   if (c->val != nullptr) return false;  // the sweep layouts carry no values
   if (p->in_mode != MIREC_IN_PRESCALED) return false;
-  if (p->in_mask != nullptr || p->row_mask != nullptr || p->row_list != nullptr) return false;
+  if (p->in_mask != nullptr && !in_mask_ok) return false;
+  if (p->row_mask != nullptr || p->row_list != nullptr) return false;
   return c->n_seg == 0;
 }
 
@@ -1421,9 +1494,34 @@ template <int D, int UNROLL>
 static int launch_head(const mirec_csr_t *c, const PropK &k, int64_t row0, hipStream_t st) {
   mirec_csr_t head = *c;
   head.n_rows = row0;
+  head.n_long = 0;  // (no segments in a launch that qualifies: nothing to finalize)
   PropK kh = k;
   kh.n_rows = row0;  // the last wave's groups past row0 - 1 stay idle
   return launch_prop<D, UNROLL>(&head, kh, 0, MIREC_IN_PRESCALED, st);
+}
+
+// Rows [row0, n_rows) of a PRESCALED launch by the row kernel: the same launch
+// on a CSR that begins at row0 (what a row indexes is shifted; x_in, in_mask
+// and the seed rows, which columns and slots index, are not).
+template <int D, int UNROLL>
+static int launch_tail(const mirec_csr_t *c, const PropK &k, int64_t row0, hipStream_t st) {
+  mirec_csr_t tail = *c;
+  tail.n_rows = c->n_rows - row0;
+  // (a launch that reaches here has no long-row segments, sweep_launch_qualifies;
+  // their lists name absolute rows and would not fit the shifted pointers)
+  if (c->n_seg != 0 || c->n_long != 0) return MIREC_ERR_ARG;
+  PropK kt = k;
+  kt.n_rows = tail.n_rows;
+  kt.rowptr += row0;
+  kt.dinv += row0;
+  if (kt.slot != nullptr) kt.slot += row0;
+  if (kt.out_mask != nullptr) kt.out_mask += row0;
+  const int64_t off = row0 * D;
+  if (kt.out != nullptr) kt.out += off;
+  if (kt.xs_out != nullptr) kt.xs_out += off;
+  if (kt.addend != nullptr) kt.addend += off;
+  if (kt.param != nullptr) kt.param += off, kt.m += off, kt.v += off;
+  return launch_prop<D, UNROLL>(&tail, kt, 0, MIREC_IN_PRESCALED, st);
 }
 
 // Item rows by the sweep kernel, rows [0, row0) by the row kernel.
@@ -1497,11 +1595,13 @@ static int32_t sweep_wave_bands(const mirec_sweep_wave_t *w) {
 }
 
 // `pace` with block = 0 (items) or 1 (users): that block's region and
-// parameters (every == 0: the block runs unpaced); `stamp`: the measurement.
+// parameters (every == 0: the block runs unpaced); `stamp`: the measurement;
+// `masked`: the in_mask forms (unscaled: checked by the caller).
 template <int D>
 static int launch_sweep_wave(const PropK &k, const mirec_sweep_wave_t *w, hipStream_t st,
                              const mirec_sweep_pace_t *pace = nullptr, int block = 0,
-                             const SweepStamp *stamp = nullptr, bool stream = false) {
+                             const SweepStamp *stamp = nullptr, bool stream = false,
+                             bool masked = false) {
   SweepWaveK s;
   s.wptr = w->wptr;
   s.slot = reinterpret_cast<const long long *>(w->slot);
@@ -1520,7 +1620,26 @@ static int launch_sweep_wave(const PropK &k, const mirec_sweep_wave_t *w, hipStr
   const bool packed = w->row_bits != 0;
   // streaming Adam has packed forms only (a cache hint: 8-byte layouts run without it)
   stream = stream && packed && k.param != nullptr;
-  if (stamp != nullptr) {
+  if (masked && (scaled || stamp != nullptr || k.in_mask == nullptr))
+    return MIREC_ERR_ARG;
+  if (masked && pace != nullptr && pace->every[block] > 0) {
+    SweepAuxK x = {};
+    x.ws = reinterpret_cast<unsigned *>(pace->ws) + block * kPaceRegionWords;
+    x.lead = pace->lead_bands[block];
+    x.every = pace->every[block];
+    x.nap = pace->nap[block];
+    const auto kernel = packed ? prop_sweep_wave_masked_aux_kernel<D, 4, kAuxPace, true>
+                               : prop_sweep_wave_masked_aux_kernel<D, 4, kAuxPace, false>;
+    const int rc = sweep_lds_allow(reinterpret_cast<const void *>(kernel), lds);
+    if (rc != MIREC_OK) return rc;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)w->grid), dim3(kSweepThreads), lds, st, k, s, x);
+  } else if (masked) {
+    const auto kernel = packed ? prop_sweep_wave_masked_kernel<D, 4, true>
+                               : prop_sweep_wave_masked_kernel<D, 4, false>;
+    const int rc = sweep_lds_allow(reinterpret_cast<const void *>(kernel), lds);
+    if (rc != MIREC_OK) return rc;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)w->grid), dim3(kSweepThreads), lds, st, k, s);
+  } else if (stamp != nullptr) {
     SweepAuxK x = {};
     x.stamps = reinterpret_cast<long long *>(stamp->stamps);
     x.meta = stamp->meta;
@@ -1581,8 +1700,9 @@ static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sw
                      mirec_stream_t stream, const mirec_drop_t *drop = nullptr,
                      const mirec_sweep_pace_t *pace = nullptr,
                      const SweepStamp *stamp = nullptr,
-                     const mirec_seed_bits_t *seeded = nullptr) {
+                     const mirec_seed_bits_t *seeded = nullptr, int32_t masked_blocks = 0) {
   MIREC_CHECK_ARG(c != nullptr && p != nullptr);
+  MIREC_CHECK_ARG((masked_blocks & ~(MIREC_SWEEP_MASKED_ITEMS | MIREC_SWEEP_MASKED_USERS)) == 0);
   if (pace != nullptr) {
     MIREC_CHECK_ARG(pace->ws != nullptr);
     for (int b = 0; b < 2; ++b)
@@ -1689,6 +1809,24 @@ static int propagate(const mirec_csr_t *c, const mirec_prop_t *p, const mirec_sw
       return launch_sweep_wave<64>(k, wu, st, pace, 1, nullptr, nt);
     return launch_head<64, 4>(c, k, wi->row0, st);
   }
+  // A launch with an in_mask whose caller asks for the masked sweep of a block
+  // (mirec_propagate_sweep_wave_masked): that block by the masked form of the
+  // wave sweep (no scales of its own), the other block's rows
+  // by the row kernel.  Everything else falls through to the row kernel.
+  if (masked_blocks != 0 && p->in_mask != nullptr && !scaled && wi != nullptr &&
+      sweep_launch_qualifies(c, p, true) &&
+      sweep_wave_valid(c, wi, wi->row0, c->n_rows - wi->row0)) {
+    const bool mi = (masked_blocks & MIREC_SWEEP_MASKED_ITEMS) != 0;
+    const bool mu = (masked_blocks & MIREC_SWEEP_MASKED_USERS) != 0 && wi->row0 > 0 &&
+                    sweep_wave_valid(c, wu, 0, wi->row0);
+    if (mi || mu) {
+      const int rc = mi ? launch_sweep_wave<64>(k, wi, st, pace, 0, nullptr, false, true)
+                        : launch_tail<64, 4>(c, k, wi->row0, st);
+      if (rc != MIREC_OK || wi->row0 == 0) return rc;
+      return mu ? launch_sweep_wave<64>(k, wu, st, pace, 1, nullptr, false, true)
+                : launch_head<64, 4>(c, k, wi->row0, st);
+    }
+  }
   if (seeded != nullptr) {  // (a launch of the seeded shape: mirec_propagate_seeded)
     switch (p->dim) {
       case 4: return launch_seeded<4, 1>(k, seeded, c->nnz, cap, st);
@@ -1747,6 +1885,15 @@ extern "C" int mirec_propagate_sweep_wave_paced(const mirec_csr_t *c, const mire
                                                 const mirec_sweep_pace_t *pace,
                                                 mirec_stream_t stream) {
   return mirec::propagate(c, p, nullptr, items, users, stream, nullptr, pace);
+}
+
+extern "C" int mirec_propagate_sweep_wave_masked(const mirec_csr_t *c, const mirec_prop_t *p,
+                                                 const mirec_sweep_wave_t *items,
+                                                 const mirec_sweep_wave_t *users,
+                                                 const mirec_sweep_pace_t *pace,
+                                                 int32_t blocks, mirec_stream_t stream) {
+  return mirec::propagate(c, p, nullptr, items, users, stream, nullptr, pace, nullptr, nullptr,
+                          blocks);
 }
 
 extern "C" int mirec_sweep_wave_stamp(const mirec_csr_t *c, const mirec_prop_t *p,

@@ -485,6 +485,29 @@ int mirec_propagate_sweep_wave_paced(const mirec_csr_t *csr, const mirec_prop_t 
                                      const mirec_sweep_wave_t *users,
                                      const mirec_sweep_pace_t *pace, mirec_stream_t stream);
 
+/* mirec_propagate_sweep_wave_paced for a launch WITH p->in_mask (a pruned
+ * step's second backward launch: every row gathers from the frontier only).
+ * `blocks` names the blocks of rows to run through the masked form of the
+ * sweep; the other block's rows run the row kernel on their row range.  The
+ * masked form needs what the full sweep needs (dim 64, PRESCALED, no values,
+ * no row_mask / row_list, no segments) and no scale vectors;
+ * a launch without in_mask, with blocks == 0 or that does not qualify is
+ * exactly mirec_propagate_sweep_wave_paced (which runs an in_mask launch as
+ * mirec_propagate does).
+ * A masked-out slot becomes padding: its term is dropped and its load reads
+ * the block's first source row instead, so masked-out rows of x_in are never
+ * read.  Bands, barriers and pacing are decided from the layout's static
+ * columns, as in the unmasked launch, whatever the mask holds.  Per row the
+ * passing terms are added in ascending source column: bitwise the unmasked
+ * sweep of an x_in whose masked-out rows are +0.0. */
+#define MIREC_SWEEP_MASKED_ITEMS 1
+#define MIREC_SWEEP_MASKED_USERS 2
+int mirec_propagate_sweep_wave_masked(const mirec_csr_t *csr, const mirec_prop_t *p,
+                                      const mirec_sweep_wave_t *items,
+                                      const mirec_sweep_wave_t *users,
+                                      const mirec_sweep_pace_t *pace, int32_t blocks,
+                                      mirec_stream_t stream);
+
 /* A measurement, not a propagation entry: the sweep launch of ONE block
  * (`layout`, items or users) with wave 0 of every workgroup noting
  * wall_clock64() at the tile's start, at each band advance and at the tile's

@@ -9,11 +9,17 @@ LightGCN d = 64 on the bench.py C2 graph in the forms of the column sweep:
                in the default --forms)
 
 and, with --sizes, the wave form at other (tile_rows, band_rows); with --pace,
-both blocks swept and one of them paced per XCD.  The forms
+both blocks swept and one of them paced per XCD.  With
+--inmask the launch is instead the second backward layer's of a pruned step
+(in_mask = the frontier F1 of one sampled batch, every row written to xs_out;
+§27) with the engine's sweep_inmask switch off / items / users / both: "off"
+is the row kernel for both blocks, "items" and "users" sweep that block with
+the masked form and leave the other to the row kernel.  The forms
 alternate inside one process; each figure is the median of --reps device-event
 timings after --warmup launches.  Prints one JSON line per form.
 
   python tools/bench_sweep_forms.py [--reps 10] [--sizes items:196x2048,...]
+  python tools/bench_sweep_forms.py --inmask [--batch 2048]
 """
 import argparse
 import json
@@ -39,6 +45,9 @@ def main():
     ap.add_argument("--pace", default="",
                     help="comma list of block:LEAD/EVERY/NAP (per-XCD pacing of that block)")
     ap.add_argument("--forms", default="row,group,wave,wave+users")
+    ap.add_argument("--inmask", action="store_true",
+                    help="time the in-masked backward launch per sweep_inmask value instead")
+    ap.add_argument("--batch", type=int, default=2048, help="--inmask: the frontier's batch")
     args = ap.parse_args()
     from furusato_recommend_amd import SyntheticBipartite
     from furusato_recommend_amd._lib import IN_PRESCALED
@@ -48,6 +57,8 @@ def main():
     ds = SyntheticBipartite(args.users, args.items, args.edges, seed=0)
     g = Graph.from_interactions(ds.trainUser, ds.trainItem, ds.n_users, ds.m_items, dev)
     D = 64
+    if args.inmask:
+        return inmask(args, g, D)
     forms = {"row": {"use_sweep": False}, "group": {"sweep_form": "group"},
              "wave": {"sweep_form": "wave", "sweep_users": False},
              "wave+users": {"sweep_form": "wave", "sweep_users": True},
@@ -103,6 +114,41 @@ def main():
                                 "passes": -(-d.n_tiles // d.grid), "slots": d.n_slots,
                                 "pad_share": round(1 - lay.n_entries / d.n_slots, 4)}
         print(json.dumps(res), flush=True)
+
+
+def inmask(args, g, D):
+    from furusato_recommend_amd._lib import IN_PRESCALED
+    from furusato_recommend_amd.engine import PropagationEngine, sample_triples
+    dev, B = g.device, args.batch
+    eng = PropagationEngine(g, D, 3, B)
+    u = torch.empty(B, dtype=torch.int32, device=dev)
+    p, n = torch.empty_like(u), torch.empty_like(u)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    sample_triples(g, B, 0, 0, u, p, n, err)
+    eng.compute_frontier(u, p, n)
+    f1 = eng.bm_hop.view(torch.uint8)[:g.n_nodes].bool()
+    share = {"users": round(float(f1[:g.n_users].float().mean()), 4),
+             "items": round(float(f1[g.n_users:].float().mean()), 4)}
+    x = torch.randn(g.n_nodes, D, device=dev) * 0.1
+    xs = torch.empty_like(x)
+    variants = ("off", "items", "users", "both")
+    times = {k: [] for k in variants}
+    for it in range(args.warmup + args.reps):
+        for name in variants:
+            eng.sweep_inmask = name
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            eng._prop(in_mode=IN_PRESCALED, x_in=x, in_mask=eng.bm_hop, xs_out=xs,
+                      direction="bwd", inmask_sweep=True)
+            e.record()
+            e.synchronize()
+            if it >= args.warmup:
+                times[name].append(s.elapsed_time(e))
+    for name in variants:
+        ts = sorted(times[name])
+        print(json.dumps({"sweep_inmask": name, "ms_median": round(statistics.median(ts), 4),
+                          "ms_min": round(ts[0], 4), "ms_max": round(ts[-1], 4),
+                          "f1_share": share}), flush=True)
 
 
 if __name__ == "__main__":

@@ -47,6 +47,12 @@ VARIANTS = {
     "full_tile280": {"sweep_packed": True, "sweep_user_tile": 280, "adam_stream": False},
     "full_tile320": {"sweep_packed": True, "sweep_user_tile": 320, "adam_stream": False},
     "full_stream": {"sweep_packed": True, "sweep_user_tile": 280, "adam_stream": True},
+    # the in-masked backward launch (launch 5 of 6) through the masked wave
+    # sweep, per block of rows
+    "inmask_off": {"sweep_inmask": "off"},
+    "inmask_items": {"sweep_inmask": "items"},
+    "inmask_users": {"sweep_inmask": "users"},
+    "inmask_both": {"sweep_inmask": "both"},
 }
 
 
