@@ -12,6 +12,7 @@ from .graph import Graph  # noqa: F401
 from .graphsage import GraphSAGE  # noqa: F401
 from .gnn import GNN  # noqa: F401
 from .tgrec import TGRec  # noqa: F401
+from .lightsage import LightSAGE  # noqa: F401
 from .lgconv import LGConv  # noqa: F401
 from . import ops  # noqa: F401  (registers torch.ops.mirec.*)
 from .lightgcn import LightGCN  # noqa: F401
@@ -21,5 +22,5 @@ from .radj import rAdjGCN  # noqa: F401
 from .sasrec import SASRec  # noqa: F401
 from .register import MODELS  # noqa: F401
 
-__all__ = ["LGConv", "LightGCN", "LightGCNSSM", "rAdjGCN", "MF", "GraphSAGE", "GNN", "TGRec", "SASRec", "Graph", "Loader", "SyntheticBipartite", "FiveCore", "MODELS",
+__all__ = ["LGConv", "LightGCN", "LightGCNSSM", "rAdjGCN", "MF", "GraphSAGE", "GNN", "TGRec", "LightSAGE", "SASRec", "Graph", "Loader", "SyntheticBipartite", "FiveCore", "MODELS",
            "MirecError", "LIB_PATH"]

@@ -292,6 +292,12 @@ SIGNATURES = {
     "mirec_fanout_mean_gather_bwd_sorted": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                                     c_float, c_uint64, c_int32, c_void_p,
                                                     c_void_p, c_size_t, c_void_p]),
+    "mirec_fanout_resmean_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                            c_int32, c_float, c_uint64, c_void_p, c_void_p]),
+    "mirec_fanout_resmean": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                     c_float, c_uint64, c_void_p, c_void_p]),
+    "mirec_fanout_resmean_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_float,
+                                         c_uint64, c_void_p, c_void_p, c_void_p]),
     "mirec_fanout_gat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_int64, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
                                  c_void_p]),

@@ -2,10 +2,12 @@
 hot path: 'lgn' = LightGCN, 'lgnssm' = LightGCNSSM, 'radj' = rAdjGCN,
 'mf' = MF, 'sage' = GraphSAGE, 'gnn' = GNN with conv = 'gat' (GATConv hops,
 the default) or 'ggnn' (GatedGraphConv hops), 'tgrec' = TGRec
-(TransformerConv hops), 'sasrec' = SASRec)."""
+(TransformerConv hops), 'lightsage' = LightSAGE (weight-free residual-mean
+hops), 'sasrec' = SASRec)."""
 from .gnn import GNN
 from .graphsage import GraphSAGE
 from .lgcnssm import LightGCNSSM
+from .lightsage import LightSAGE
 from .lightgcn import LightGCN
 from .mf import MF
 from .radj import rAdjGCN
@@ -20,5 +22,6 @@ MODELS = {
     "sage": GraphSAGE,
     "gnn": GNN,
     "tgrec": TGRec,
+    "lightsage": LightSAGE,
     "sasrec": SASRec,
 }

@@ -295,8 +295,10 @@ int mirec_edge_keep_mask(const int64_t *rowptr, const int32_t *col, int64_t n_ro
  * NaN included).  Element index:
  *   (t*k + c) * dim + col   mirec_fanout_mean and its backward,
  *                           mirec_fanout_mean_gather and both its backwards,
- *                           the mean groups of mirec_table_grad_*: column col
- *                           of child c of target t
+ *                           the mean groups of mirec_table_grad_*,
+ *                           mirec_fanout_resmean_gather, mirec_fanout_resmean
+ *                           and mirec_fanout_resmean_bwd: column col of child
+ *                           c of target t
  *   row * d + col           mirec_resnorm_fwd / _bwd, mirec_gemm_resnorm,
  *                           mirec_gemm_nn_resnorm_bwd
  * seed_base (row tail only; device, may be NULL): when given, the launch uses
@@ -1117,6 +1119,37 @@ int mirec_fanout_mean_gather_bwd_sorted(const float *grad_out, const int32_t *id
                                         float dropout_p, uint64_t seed, int32_t n_rows,
                                         float *table_grad, void *workspace,
                                         size_t workspace_bytes, mirec_stream_t stream);
+
+/* LightSAGE hop (model/lightsage.py:274-290: no weights, no ReLU): for target
+ * t with the k child slots t*k .. t*k + k - 1,
+ *   out[t] = self_t + (1 / cnt_t) * sum over the valid slots c, in slot order,
+ *            of dropout(child row of slot t*k + c)
+ * cnt_t = the number of valid slots; a target without one gets self_t.  The
+ * dropout is the element dropout stated above at element index (t*k + c)*dim
+ * + col.  dim % 4 == 0, k >= 1, float rows 16-byte aligned; bad arguments
+ * (dropout_p outside [0, 1), NaN included) return MIREC_ERR_ARG and launch
+ * nothing.
+ * _gather (the first layer, nothing materialised): self_t = table[self_ids[t]]
+ * (a zero row for an id < 0), slot e is valid iff child_ids[e] >= 0 and its
+ * row is table[child_ids[e]].
+ * The plain form: self_t = x_self[t], slot e's row is x_child[e], valid iff
+ * valid[e] >= 0 (all valid if valid == NULL).  On x_child = the gathered
+ * table rows and x_self = the gathered self rows the two forms give the same
+ * bits. */
+int mirec_fanout_resmean_gather(const float *table, const int32_t *self_ids,
+                                const int32_t *child_ids, int64_t n_targets, int32_t k,
+                                int32_t dim, float dropout_p, uint64_t seed, float *out,
+                                mirec_stream_t stream);
+int mirec_fanout_resmean(const float *x_self, const float *x_child, const int32_t *valid,
+                         int64_t n_targets, int32_t k, int32_t dim, float dropout_p,
+                         uint64_t seed, float *out, mirec_stream_t stream);
+
+/* Backward of both forms: grad_self[t] = grad_out[t]; grad_child[t*k + c] =
+ * mask * scale * grad_out[t] / cnt_t, a zero row for an invalid slot.  Both
+ * outputs are written, not added to. */
+int mirec_fanout_resmean_bwd(const float *grad_out, const int32_t *valid, int64_t n_targets,
+                             int32_t k, int32_t dim, float dropout_p, uint64_t seed,
+                             float *grad_self, float *grad_child, mirec_stream_t stream);
 
 /* Graph-attention hop (PyG GATConv, concat=True, add_self_loops=True, no
  * attention dropout; model/gnn.py:196-206) on the same fixed-fanout tree.
