@@ -17,11 +17,10 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
+#include "seedrun.h"
 #include "smallsort.h"
 
 namespace mirec {
-
-constexpr int kWaves = 4;
 
 template <int D>
 __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void bpr_forward_kernel(
@@ -33,7 +32,7 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void bpr_forward_kernel(
   constexpr int G = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const int sub = lane % LPR;
-  const int64_t t = ((int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6)) * G + lane / LPR;
+  const int64_t t = ((int64_t)blockIdx.x * kSeedWaves + (threadIdx.x >> 6)) * G + lane / LPR;
   const bool live = t < batch;
   const int64_t tt = live ? t : 0;
   const int64_t u = users[tt];
@@ -116,77 +115,29 @@ __global__ __launch_bounds__(256) void seed_accum_kernel(
     const int32_t *__restrict__ neg, const float *__restrict__ coef,
     const int32_t *__restrict__ keys_sorted, const int32_t *__restrict__ vals_sorted,
     float decay, float grad_scale, float layer_div, float *seed_p, float *seed_e) {
-  constexpr int LPR = D / 4;
-  constexpr int G = 64 / LPR;
-  const int lane = threadIdx.x & 63;
-  const int sub = lane % LPR;
   const int64_t n = 3 * batch;
-  const int64_t q = ((int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6)) * G + lane / LPR;
+  const int64_t q = seed_run_pos<D>();
   if (q >= n) return;
   const int32_t node = keys_sorted[q];
   if (q > 0 && keys_sorted[q - 1] == node) return;  // not the head of its run
-  // The run is walked LPR entries per round: lane j decodes entry q0 + j
-  // (source rows and coefficients), then the group loads the rows 8 at a
-  // time and adds them in entry order — the serial walk's exact sequence of
-  // fmas (bitwise equal) without one dependent index chain per entry (a
-  // Zipf-popular item is hundreds of entries of a batch).
-  const int base = lane - sub;
-  const unsigned long long low = LPR == 64 ? ~0ull : ((1ull << LPR) - 1ull);
-  const unsigned long long gmask = low << base;
-  float4 gp = f4_zero();
-  int cnt = 0;
-  for (int64_t q0 = q;; q0 += LPR) {
-    const int64_t qj = q0 + sub;
-    const bool in = qj < n && keys_sorted[qj] == node;
-    int32_t ra = -1, rb = -1;
-    float ca = 0.f, cb = 0.f;
-    if (in) {
-      const int64_t occ = vals_sorted[qj];
-      const int64_t role = occ / batch;
-      const int64_t t = occ - role * batch;
-      const float c = coef[t];
-      if (role == 0) {  // the negative's row, then the positive's
-        ra = (int32_t)(n_users + neg[t]);
-        ca = c;
-        rb = (int32_t)(n_users + pos[t]);
-        cb = -c;
-      } else {
-        ra = users[t];
-        ca = role == 1 ? -c : c;
-      }
-    }
-    const unsigned long long bal = (__ballot(in) & gmask) >> base;
-    const int m = bal == low ? LPR : (int)__builtin_ctzll(~bal);
-    for (int u0 = 0; u0 < m; u0 += 8) {
-      float4 xa[8], xb[8];
-      float wa[8], wb[8];
-      bool hb[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int src = base + ((u0 + u) & (LPR - 1));
-        const int32_t a_row = __shfl(ra, src), b_row = __shfl(rb, src);
-        wa[u] = __shfl(ca, src);
-        wb[u] = __shfl(cb, src);
-        const bool ok = u0 + u < m;
-        xa[u] = ok ? ld4(out + (int64_t)a_row * D + sub * 4) : f4_zero();
-        hb[u] = ok && b_row >= 0;
-        xb[u] = hb[u] ? ld4(out + (int64_t)b_row * D + sub * 4) : f4_zero();
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        if (u0 + u >= m) break;
-        gp = f4_fma(wa[u], xa[u], gp);
-        if (hb[u]) gp = f4_fma(wb[u], xb[u], gp);
-      }
-    }
-    cnt += m;
-    if (m < LPR) break;
-  }
-  const float4 e = ld4(emb + (int64_t)node * D + sub * 4);
-  float re = decay * ((float)cnt / (float)batch);
-  if (grad_scale != 1.f) re *= grad_scale;
-  st4(seed_p + q * D + sub * 4, f4_div(gp, layer_div));
-  st4(seed_e + q * D + sub * 4, f4_scale(re, e));
+  seed_run_walk<D, 2>(
+      q, node, n, batch, emb, keys_sorted, vals_sorted, decay, grad_scale, layer_div, seed_p,
+      seed_e,
+      [=](int64_t occ, int32_t(&row)[2], float(&w)[2]) {
+        const int64_t role = occ / batch;
+        const int64_t t = occ - role * batch;
+        const float c = coef[t];
+        if (role == 0) {  // the negative's row, then the positive's
+          row[0] = (int32_t)(n_users + neg[t]);
+          w[0] = c;
+          row[1] = (int32_t)(n_users + pos[t]);
+          w[1] = -c;
+        } else {
+          row[0] = users[t];
+          w[0] = role == 1 ? -c : c;
+        }
+      },
+      [=](int32_t r) { return out + (int64_t)r * D; });
 }
 
 __global__ void seed_reset_kernel(int32_t *slot, const int32_t *keys_sorted, int64_t n) {
@@ -236,7 +187,7 @@ __global__ __launch_bounds__(256) void merge_accum_kernel(const int32_t *__restr
   constexpr int G = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const int sub = lane % LPR;
-  const int64_t q = ((int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6)) * G + lane / LPR;
+  const int64_t q = ((int64_t)blockIdx.x * kSeedWaves + (threadIdx.x >> 6)) * G + lane / LPR;
   if (q >= n) return;
   const int32_t node = keys_sorted[q];
   if (node < 0) return;
@@ -268,20 +219,17 @@ static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 // one / two-launch sort (smallsort.hip: the C2 step's 6 144 seeds in one
 // launch instead of the radix sort's six), above it the device library's
 // radix sort; both return the stable order.
-static int sort_temp_bytes(int64_t n3, int64_t n_nodes, size_t *bytes) {
-  if (n3 <= kSmallSortMax) {
-    *bytes = small_sort_workspace(n3);
-    return MIREC_OK;
-  }
+int seed_ws_layout(int64_t n, int64_t n_nodes, size_t *sort_bytes, size_t *total) {
   size_t tb = 0;
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(
-      nullptr, tb, (const int32_t *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr,
-      (int32_t *)nullptr, (int)n3, 0, end_bit_for(n_nodes), (hipStream_t)0);
-  if (e != hipSuccess) {
-    g_last_hip_error = (int)e;
-    return MIREC_ERR_HIP;
+  if (n <= kSmallSortMax) {
+    tb = small_sort_workspace(n);
+  } else {
+    MIREC_HIP(hipcub::DeviceRadixSort::SortPairs(
+        nullptr, tb, (const int32_t *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr,
+        (int32_t *)nullptr, (int)n, 0, end_bit_for(n_nodes), (hipStream_t)0));
   }
-  *bytes = tb;
+  *sort_bytes = tb;
+  *total = align_up(tb) + align_up((size_t)n * sizeof(int32_t));
   return MIREC_OK;
 }
 
@@ -294,32 +242,31 @@ static hipError_t sort_pairs(void *ws, size_t tb, const int32_t *keys, int32_t *
                                             0, end_bit_for(n_nodes), st);
 }
 
+int seed_sort_heads(const int32_t *keys, const int32_t *vals, int64_t n, int64_t n_nodes,
+                    void *ws, size_t ws_bytes, int32_t *keys_sorted, int32_t **vals_sorted,
+                    int32_t *slot, hipStream_t st) {
+  size_t tb = 0, need = 0;
+  int rc = seed_ws_layout(n, n_nodes, &tb, &need);
+  if (rc != MIREC_OK) return rc;
+  if (ws_bytes < need) return MIREC_ERR_WORKSPACE;
+  *vals_sorted = reinterpret_cast<int32_t *>(static_cast<char *>(ws) + align_up(tb));
+  MIREC_HIP(sort_pairs(ws, tb, keys, keys_sorted, vals, *vals_sorted, n, n_nodes, st));
+  hipLaunchKernelGGL(seed_heads_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                     keys_sorted, n, slot);
+  MIREC_LAUNCH_CHECK();
+  return MIREC_OK;
+}
+
 template <int D>
 static int launch_bpr_forward(const float *out, const float *emb, int64_t n_users, int64_t batch,
                               const int32_t *users, const int32_t *pos, const int32_t *neg,
                               float grad_scale, float *coef, float *sp, float *reg,
                               int32_t *keys, int32_t *vals, hipStream_t st) {
   constexpr int G = 64 / (D / 4);
-  const int64_t per_block = (int64_t)kWaves * G;
+  const int64_t per_block = (int64_t)kSeedWaves * G;
   const int64_t blocks = (batch + per_block - 1) / per_block;
   hipLaunchKernelGGL((bpr_forward_kernel<D>), dim3(blocks), dim3(256), 0, st, out, emb, n_users,
                      batch, users, pos, neg, grad_scale, coef, sp, reg, keys, vals);
-  MIREC_LAUNCH_CHECK();
-  return MIREC_OK;
-}
-
-template <int D>
-static int launch_seed_accum(const float *out, const float *emb, int64_t n_users, int64_t batch,
-                             const int32_t *users, const int32_t *pos, const int32_t *neg,
-                             const float *coef, const int32_t *ks, const int32_t *vs, float decay,
-                             float grad_scale, float layer_div, float *seed_p, float *seed_e,
-                             hipStream_t st) {
-  constexpr int G = 64 / (D / 4);
-  const int64_t per_block = (int64_t)kWaves * G;
-  const int64_t blocks = (3 * batch + per_block - 1) / per_block;
-  hipLaunchKernelGGL((seed_accum_kernel<D>), dim3(blocks), dim3(256), 0, st, out, emb, n_users,
-                     batch, users, pos, neg, coef, ks, vs, decay, grad_scale, layer_div, seed_p,
-                     seed_e);
   MIREC_LAUNCH_CHECK();
   return MIREC_OK;
 }
@@ -363,10 +310,7 @@ extern "C" int mirec_bpr_seed_workspace(int64_t batch, int64_t n_nodes, size_t *
   using namespace mirec;
   MIREC_CHECK_ARG(bytes != nullptr && batch > 0 && n_nodes > 0);
   size_t tb = 0;
-  int rc = sort_temp_bytes(3 * batch, n_nodes, &tb);
-  if (rc != MIREC_OK) return rc;
-  *bytes = align_up(tb) + align_up((size_t)3 * batch * sizeof(int32_t));
-  return MIREC_OK;
+  return seed_ws_layout(3 * batch, n_nodes, &tb, bytes);
 }
 
 extern "C" int mirec_bpr_seed(const float *out, const float *emb, int64_t n_nodes, int64_t n_users,
@@ -383,24 +327,16 @@ extern "C" int mirec_bpr_seed(const float *out, const float *emb, int64_t n_node
   MIREC_CHECK_ARG(batch > 0 && n_layers >= 0 && n_nodes > n_users);
   if (!dim_supported(dim)) return MIREC_ERR_DIM;
   const int64_t n3 = 3 * batch;
-  size_t tb = 0;
-  int rc = sort_temp_bytes(n3, n_nodes, &tb);
-  if (rc != MIREC_OK) return rc;
-  const size_t need = align_up(tb) + align_up((size_t)n3 * sizeof(int32_t));
-  if (workspace_bytes < need) return MIREC_ERR_WORKSPACE;
-  char *ws = static_cast<char *>(workspace);
-  int32_t *vals_sorted = reinterpret_cast<int32_t *>(ws + align_up(tb));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  size_t tb2 = tb;
-  MIREC_HIP(sort_pairs(ws, tb2, keys, keys_sorted, vals, vals_sorted, n3, n_nodes, st));
-  hipLaunchKernelGGL(seed_heads_kernel, dim3((n3 + 255) / 256), dim3(256), 0, st, keys_sorted, n3,
-                     slot);
-  MIREC_LAUNCH_CHECK();
+  int32_t *vals_sorted = nullptr;
+  int rc = seed_sort_heads(keys, vals, n3, n_nodes, workspace, workspace_bytes, keys_sorted,
+                           &vals_sorted, slot, st);
+  if (rc != MIREC_OK) return rc;
   const float layer_div = (float)(n_layers + 1);
   switch (dim) {
 #define C(DD) \
   case DD:    \
-    return launch_seed_accum<DD>(out, emb, n_users, batch, users, pos, neg, coef, keys_sorted, vals_sorted, decay, grad_scale, layer_div, seed_p, seed_e, st);
+    return launch_seed_accum<DD>(seed_accum_kernel<DD>, n3, st, out, emb, n_users, batch, users, pos, neg, coef, keys_sorted, vals_sorted, decay, grad_scale, layer_div, seed_p, seed_e);
     C(4) C(8) C(16) C(32) C(64) C(128) C(256)
 #undef C
   }
@@ -434,10 +370,9 @@ extern "C" int mirec_seed_merge_workspace(int64_t n, int64_t n_nodes, size_t *by
   using namespace mirec;
   MIREC_CHECK_ARG(bytes && n > 0 && n_nodes > 0 && n < INT32_MAX);
   size_t tb = 0;
-  int rc = sort_temp_bytes(n, n_nodes + 1, &tb);
-  if (rc != MIREC_OK) return rc;
-  *bytes = align_up(tb) + 2 * align_up((size_t)n * sizeof(int32_t));
-  return MIREC_OK;
+  int rc = seed_ws_layout(n, n_nodes + 1, &tb, bytes);
+  if (rc == MIREC_OK) *bytes += align_up((size_t)n * sizeof(int32_t));  // the second index block
+  return rc;
 }
 
 template <int D>
@@ -445,7 +380,7 @@ static int launch_merge_accum(const int32_t *ks, const int32_t *is, int64_t n, c
                               const float *re, float *sp, float *se, hipStream_t st) {
   using namespace mirec;
   constexpr int G = 64 / (D / 4);
-  const int64_t per_block = (int64_t)kWaves * G;
+  const int64_t per_block = (int64_t)kSeedWaves * G;
   hipLaunchKernelGGL((merge_accum_kernel<D>), dim3((n + per_block - 1) / per_block), dim3(256), 0,
                      st, ks, is, n, rp, re, sp, se);
   MIREC_LAUNCH_CHECK();
@@ -461,11 +396,10 @@ extern "C" int mirec_seed_merge(const int32_t *keys_packed, const float *rows_p,
   MIREC_CHECK_ARG(keys_packed && rows_p && rows_e && slot && seed_p && seed_e && keys_sorted &&
                   workspace && n > 0 && n < INT32_MAX && n_nodes > 0 && n_nodes < INT32_MAX);
   if (!dim_supported(dim)) return MIREC_ERR_DIM;
-  size_t tb = 0;
-  int rc = sort_temp_bytes(n, n_nodes + 1, &tb);
+  size_t tb = 0, need = 0;
+  int rc = seed_ws_layout(n, n_nodes + 1, &tb, &need);
   if (rc != MIREC_OK) return rc;
-  const size_t need = align_up(tb) + 2 * align_up((size_t)n * sizeof(int32_t));
-  if (workspace_bytes < need) return MIREC_ERR_WORKSPACE;
+  if (workspace_bytes < need + align_up((size_t)n * sizeof(int32_t))) return MIREC_ERR_WORKSPACE;
   char *ws = static_cast<char *>(workspace);
   int32_t *idx_in = reinterpret_cast<int32_t *>(ws + align_up(tb));
   int32_t *idx_sorted = reinterpret_cast<int32_t *>(ws + align_up(tb) + align_up(n * 4));

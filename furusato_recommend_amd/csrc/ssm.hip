@@ -24,16 +24,12 @@
 // seed_p[q] = that / (L+1), seed_e[q] = decay * (#occurrences) e_node / B *
 // grad_scale, slot[node] = q — bpr.hip's seed rows, for PropagationEngine's
 // backward.  No float atomics: every sum has one fixed order.
-#include <hipcub/hipcub.hpp>
-
 #include <cmath>
 
 #include "common.h"
-#include "smallsort.h"
+#include "seedrun.h"
 
 namespace mirec {
-
-constexpr int kSsmWaves = 4;
 
 __global__ __launch_bounds__(256) void ssm_keys_kernel(const int32_t *__restrict__ users,
                                                        const int32_t *__restrict__ pos,
@@ -56,7 +52,7 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void ssm_forward_kernel(
   constexpr int G = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const int sub = lane % LPR;
-  const int64_t t = ((int64_t)blockIdx.x * kSsmWaves + (threadIdx.x >> 6)) * G + lane / LPR;
+  const int64_t t = ((int64_t)blockIdx.x * kSeedWaves + (threadIdx.x >> 6)) * G + lane / LPR;
   const bool live = t < batch;
   const int64_t tt = live ? t : 0;
   const int K = n_neg;
@@ -122,13 +118,9 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void ssm_forward_kernel(
   }
 }
 
-__global__ void ssm_heads_kernel(const int32_t *keys_sorted, int64_t n, int32_t *slot) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= n) return;
-  const int32_t k = keys_sorted[q];
-  if (q == 0 || keys_sorted[q - 1] != k) slot[k] = (int32_t)q;
-}
-
+// seedrun.h's run walk with this loss's decode: every occurrence is one source
+// row times one coefficient, a row of `out` (index >= 0) or row t of g_u
+// (stored as ~t).
 template <int D>
 __global__ __launch_bounds__(256) void ssm_seed_accum_kernel(
     const float *__restrict__ out, const float *__restrict__ emb, int64_t batch, int32_t n_neg,
@@ -136,97 +128,28 @@ __global__ __launch_bounds__(256) void ssm_seed_accum_kernel(
     const float *__restrict__ coef_pos, const float *__restrict__ g_u,
     const int32_t *__restrict__ keys_sorted, const int32_t *__restrict__ vals_sorted, float decay,
     float grad_scale, float layer_div, float *seed_p, float *seed_e) {
-  constexpr int LPR = D / 4;
-  constexpr int G = 64 / LPR;
-  const int lane = threadIdx.x & 63;
-  const int sub = lane % LPR;
   const int64_t n = (2 + (int64_t)n_neg) * batch;
-  const int64_t q = ((int64_t)blockIdx.x * kSsmWaves + (threadIdx.x >> 6)) * G + lane / LPR;
+  const int64_t q = seed_run_pos<D>();
   if (q >= n) return;
   const int32_t node = keys_sorted[q];
   if (q > 0 && keys_sorted[q - 1] == node) return;  // not the head of its run
-  // The run is walked LPR entries per round (bpr.hip's seed_accum_kernel):
-  // lane j decodes entry q0 + j into one source row and one coefficient —
-  // a row of `out` (index >= 0) or row t of g_u (stored as ~t) — then the
-  // group loads the rows 8 at a time and adds them in entry order.
-  const int base = lane - sub;
-  const unsigned long long low = LPR == 64 ? ~0ull : ((1ull << LPR) - 1ull);
-  const unsigned long long gmask = low << base;
-  float4 gp = f4_zero();
-  int cnt = 0;
-  for (int64_t q0 = q;; q0 += LPR) {
-    const int64_t qj = q0 + sub;
-    const bool in = qj < n && keys_sorted[qj] == node;
-    int32_t ra = 0;
-    float ca = 0.f;
-    if (in) {
-      const int64_t occ = vals_sorted[qj];
-      if (occ < batch) {
-        ra = ~(int32_t)occ;
-        ca = 1.f;
-      } else if (occ < 2 * batch) {
-        ra = users[occ - batch];
-        ca = -coef_pos[occ - batch];
-      } else {
-        const int64_t j = occ - 2 * batch;
-        ra = users[j / n_neg];
-        ca = coef[j];
-      }
-    }
-    const unsigned long long bal = (__ballot(in) & gmask) >> base;
-    const int m = bal == low ? LPR : (int)__builtin_ctzll(~bal);
-    for (int u0 = 0; u0 < m; u0 += 8) {
-      float4 xa[8];
-      float wa[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int src = base + ((u0 + u) & (LPR - 1));
-        const int32_t a_row = __shfl(ra, src);
-        wa[u] = __shfl(ca, src);
-        const float *row = a_row >= 0 ? out + (int64_t)a_row * D : g_u + (int64_t)(~a_row) * D;
-        xa[u] = u0 + u < m ? ld4(row + sub * 4) : f4_zero();
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        if (u0 + u >= m) break;
-        gp = f4_fma(wa[u], xa[u], gp);
-      }
-    }
-    cnt += m;
-    if (m < LPR) break;
-  }
-  const float4 e = ld4(emb + (int64_t)node * D + sub * 4);
-  float re = decay * ((float)cnt / (float)batch);
-  if (grad_scale != 1.f) re *= grad_scale;
-  st4(seed_p + q * D + sub * 4, f4_div(gp, layer_div));
-  st4(seed_e + q * D + sub * 4, f4_scale(re, e));
-}
-
-static int ssm_end_bit(int64_t n_nodes) {
-  int b = 1;
-  while (b < 31 && ((int64_t)1 << b) < n_nodes) ++b;
-  return b;
-}
-
-static size_t ssm_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// The (node, occurrence) sort, as mirec_bpr_seed's: the library's small sort
-// up to kSmallSortMax pairs, the device library's radix sort above it.
-static int ssm_sort_bytes(int64_t n, int64_t n_nodes, size_t *bytes) {
-  if (n <= kSmallSortMax) {
-    *bytes = small_sort_workspace(n);
-    return MIREC_OK;
-  }
-  size_t tb = 0;
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(
-      nullptr, tb, (const int32_t *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr,
-      (int32_t *)nullptr, (int)n, 0, ssm_end_bit(n_nodes), (hipStream_t)0);
-  if (e != hipSuccess) {
-    g_last_hip_error = (int)e;
-    return MIREC_ERR_HIP;
-  }
-  *bytes = tb;
-  return MIREC_OK;
+  seed_run_walk<D, 1>(
+      q, node, n, batch, emb, keys_sorted, vals_sorted, decay, grad_scale, layer_div, seed_p,
+      seed_e,
+      [=](int64_t occ, int32_t(&row)[1], float(&w)[1]) {
+        if (occ < batch) {
+          row[0] = ~(int32_t)occ;
+          w[0] = 1.f;
+        } else if (occ < 2 * batch) {
+          row[0] = users[occ - batch];
+          w[0] = -coef_pos[occ - batch];
+        } else {
+          const int64_t j = occ - 2 * batch;
+          row[0] = users[j / n_neg];
+          w[0] = coef[j];
+        }
+      },
+      [=](int32_t r) { return r >= 0 ? out + (int64_t)r * D : g_u + (int64_t)(~r) * D; });
 }
 
 template <int D>
@@ -236,27 +159,11 @@ static int launch_ssm_forward(const float *out, const float *emb, int64_t n_user
                               float *coef_pos, float *terms, float *reg, float *g_u,
                               int32_t *keys, int32_t *vals, hipStream_t st) {
   constexpr int G = 64 / (D / 4);
-  const int64_t per_block = (int64_t)kSsmWaves * G;
+  const int64_t per_block = (int64_t)kSeedWaves * G;
   const int64_t blocks = (batch + per_block - 1) / per_block;
   hipLaunchKernelGGL((ssm_forward_kernel<D>), dim3(blocks), dim3(256), 0, st, out, emb, n_users,
                      batch, n_neg, users, pos, neg, temp, grad_scale, coef, coef_pos, terms, reg,
                      g_u, keys, vals);
-  MIREC_LAUNCH_CHECK();
-  return MIREC_OK;
-}
-
-template <int D>
-static int launch_ssm_seed_accum(const float *out, const float *emb, int64_t batch, int32_t n_neg,
-                                 const int32_t *users, const float *coef, const float *coef_pos,
-                                 const float *g_u, const int32_t *ks, const int32_t *vs,
-                                 float decay, float grad_scale, float layer_div, float *seed_p,
-                                 float *seed_e, hipStream_t st) {
-  constexpr int G = 64 / (D / 4);
-  const int64_t per_block = (int64_t)kSsmWaves * G;
-  const int64_t n = (2 + (int64_t)n_neg) * batch;
-  hipLaunchKernelGGL((ssm_seed_accum_kernel<D>), dim3((n + per_block - 1) / per_block), dim3(256),
-                     0, st, out, emb, batch, n_neg, users, coef, coef_pos, g_u, ks, vs, decay,
-                     grad_scale, layer_div, seed_p, seed_e);
   MIREC_LAUNCH_CHECK();
   return MIREC_OK;
 }
@@ -317,10 +224,7 @@ extern "C" int mirec_ssm_seed_workspace(int64_t batch, int32_t n_neg, int64_t n_
   int64_t n = 0;
   MIREC_CHECK_ARG(bytes != nullptr && n_nodes > 0 && ssm_pairs(batch, n_neg, &n));
   size_t tb = 0;
-  int rc = ssm_sort_bytes(n, n_nodes, &tb);
-  if (rc != MIREC_OK) return rc;
-  *bytes = ssm_align(tb) + ssm_align((size_t)n * sizeof(int32_t));
-  return MIREC_OK;
+  return seed_ws_layout(n, n_nodes, &tb, bytes);
 }
 
 extern "C" int mirec_ssm_seed(const float *out, const float *emb, int64_t n_nodes, int64_t n_users,
@@ -337,29 +241,16 @@ extern "C" int mirec_ssm_seed(const float *out, const float *emb, int64_t n_node
   MIREC_CHECK_ARG(ssm_pairs(batch, n_neg, &n));
   MIREC_CHECK_ARG(n_layers >= 0 && n_users > 0 && n_nodes > n_users && n_nodes < INT32_MAX);
   if (!dim_supported(dim)) return MIREC_ERR_ARG;
-  size_t tb = 0;
-  int rc = ssm_sort_bytes(n, n_nodes, &tb);
-  if (rc != MIREC_OK) return rc;
-  const size_t need = ssm_align(tb) + ssm_align((size_t)n * sizeof(int32_t));
-  if (workspace_bytes < need) return MIREC_ERR_WORKSPACE;
-  char *ws = static_cast<char *>(workspace);
-  int32_t *vals_sorted = reinterpret_cast<int32_t *>(ws + ssm_align(tb));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (n <= kSmallSortMax) {
-    MIREC_HIP(small_sort_pairs(ws, tb, keys, keys_sorted, vals, vals_sorted, n, st));
-  } else {
-    size_t tb2 = tb;
-    MIREC_HIP(hipcub::DeviceRadixSort::SortPairs(ws, tb2, keys, keys_sorted, vals, vals_sorted,
-                                                 (int)n, 0, ssm_end_bit(n_nodes), st));
-  }
-  hipLaunchKernelGGL(ssm_heads_kernel, dim3((n + 255) / 256), dim3(256), 0, st, keys_sorted, n,
-                     slot);
-  MIREC_LAUNCH_CHECK();
+  int32_t *vals_sorted = nullptr;
+  int rc = seed_sort_heads(keys, vals, n, n_nodes, workspace, workspace_bytes, keys_sorted,
+                           &vals_sorted, slot, st);
+  if (rc != MIREC_OK) return rc;
   const float layer_div = (float)(n_layers + 1);
   switch (dim) {
 #define C(DD) \
   case DD:    \
-    return launch_ssm_seed_accum<DD>(out, emb, batch, n_neg, users, coef, coef_pos, g_u, keys_sorted, vals_sorted, decay, grad_scale, layer_div, seed_p, seed_e, st);
+    return launch_seed_accum<DD>(ssm_seed_accum_kernel<DD>, n, st, out, emb, batch, n_neg, users, coef, coef_pos, g_u, keys_sorted, vals_sorted, decay, grad_scale, layer_div, seed_p, seed_e);
     C(4) C(8) C(16) C(32) C(64) C(128) C(256)
 #undef C
   }

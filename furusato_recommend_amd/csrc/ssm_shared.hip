@@ -35,16 +35,13 @@
 //   shared occurrence:  1 * g[B + j]
 // seed_p[q] = that / (L+1), seed_e[q] = decay * (#occurrences) e_node / B *
 // grad_scale, slot[node] = q: ssm.hip's seed rows.
-#include <hipcub/hipcub.hpp>
-
 #include <cmath>
 
 #include "common.h"
-#include "smallsort.h"
+#include "seedrun.h"
 
 namespace mirec {
 
-constexpr int kShWaves = 4;
 constexpr int kShTile = 64;  // scores: pairs x slots per workgroup
 constexpr int kShUnroll = 8;  // rows: elements per lane and round
 
@@ -150,7 +147,7 @@ __global__ __launch_bounds__(256) MIREC_NO_PK_F32 void ssh_rows_kernel(
     int32_t *keys, int32_t *vals) {
   constexpr int LPR = D / 4;
   const int lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * kShWaves + (threadIdx.x >> 6);
+  const int64_t i = (int64_t)blockIdx.x * kSeedWaves + (threadIdx.x >> 6);
   if (i >= batch + m) return;
   const bool has = lane < LPR;
   if (i >= batch) {
@@ -388,14 +385,7 @@ __global__ __launch_bounds__(1024) void ssh_loss_kernel(const float *terms, cons
   }
 }
 
-__global__ void ssh_heads_kernel(const int32_t *keys_sorted, int64_t n, int32_t *slot) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= n) return;
-  const int32_t k = keys_sorted[q];
-  if (q == 0 || keys_sorted[q - 1] != k) slot[k] = (int32_t)q;
-}
-
-// ssm.hip's run walk with this loss's decode: every occurrence is one source
+// seedrun.h's run walk with this loss's decode: every occurrence is one source
 // row times one coefficient, a row of `out` (index >= 0) or row r of g
 // (stored as ~r).
 template <int D>
@@ -405,91 +395,27 @@ __global__ __launch_bounds__(256) void ssh_seed_accum_kernel(
     const float *__restrict__ g, const int32_t *__restrict__ keys_sorted,
     const int32_t *__restrict__ vals_sorted, float decay, float grad_scale, float layer_div,
     float *seed_p, float *seed_e) {
-  constexpr int LPR = D / 4;
-  constexpr int G = 64 / LPR;
-  const int lane = threadIdx.x & 63;
-  const int sub = lane % LPR;
   const int64_t n = 2 * batch + m;
-  const int64_t q = ((int64_t)blockIdx.x * kShWaves + (threadIdx.x >> 6)) * G + lane / LPR;
+  const int64_t q = seed_run_pos<D>();
   if (q >= n) return;
   const int32_t node = keys_sorted[q];
   if (q > 0 && keys_sorted[q - 1] == node) return;  // not the head of its run
-  const int base = lane - sub;
-  const unsigned long long low = LPR == 64 ? ~0ull : ((1ull << LPR) - 1ull);
-  const unsigned long long gmask = low << base;
-  float4 gp = f4_zero();
-  int cnt = 0;
-  for (int64_t q0 = q;; q0 += LPR) {
-    const int64_t qj = q0 + sub;
-    const bool in = qj < n && keys_sorted[qj] == node;
-    int32_t ra = 0;
-    float ca = 0.f;
-    if (in) {
-      const int64_t occ = vals_sorted[qj];
-      if (occ < batch) {
-        ra = ~(int32_t)occ;
-        ca = 1.f;
-      } else if (occ < 2 * batch) {
-        ra = users[occ - batch];
-        ca = -coef_pos[occ - batch];
-      } else {
-        ra = ~(int32_t)(occ - batch);  // g[B + j], j = occ - 2B
-        ca = 1.f;
-      }
-    }
-    const unsigned long long bal = (__ballot(in) & gmask) >> base;
-    const int cn = bal == low ? LPR : (int)__builtin_ctzll(~bal);
-    for (int u0 = 0; u0 < cn; u0 += 8) {
-      float4 xa[8];
-      float wa[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int src = base + ((u0 + u) & (LPR - 1));
-        const int32_t a_row = __shfl(ra, src);
-        wa[u] = __shfl(ca, src);
-        const float *row = a_row >= 0 ? out + (int64_t)a_row * D : g + (int64_t)(~a_row) * D;
-        xa[u] = u0 + u < cn ? ld4(row + sub * 4) : f4_zero();
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        if (u0 + u >= cn) break;
-        gp = f4_fma(wa[u], xa[u], gp);
-      }
-    }
-    cnt += cn;
-    if (cn < LPR) break;
-  }
-  const float4 e = ld4(emb + (int64_t)node * D + sub * 4);
-  float re = decay * ((float)cnt / (float)batch);
-  if (grad_scale != 1.f) re *= grad_scale;
-  st4(seed_p + q * D + sub * 4, f4_div(gp, layer_div));
-  st4(seed_e + q * D + sub * 4, f4_scale(re, e));
-}
-
-static int ssh_end_bit(int64_t n_nodes) {
-  int b = 1;
-  while (b < 31 && ((int64_t)1 << b) < n_nodes) ++b;
-  return b;
-}
-
-static size_t ssh_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// The (node, occurrence) sort, as mirec_ssm_seed's.
-static int ssh_sort_bytes(int64_t n, int64_t n_nodes, size_t *bytes) {
-  if (n <= kSmallSortMax) {
-    *bytes = small_sort_workspace(n);
-    return MIREC_OK;
-  }
-  size_t tb = 0;
-  hipError_t e = hipcub::DeviceRadixSort::SortPairs(
-      nullptr, tb, (const int32_t *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr,
-      (int32_t *)nullptr, (int)n, 0, ssh_end_bit(n_nodes), (hipStream_t)0);
-  if (e != hipSuccess) {
-    g_last_hip_error = (int)e;
-    return MIREC_ERR_HIP;
-  }
-  *bytes = tb;
-  return MIREC_OK;
+  seed_run_walk<D, 1>(
+      q, node, n, batch, emb, keys_sorted, vals_sorted, decay, grad_scale, layer_div, seed_p,
+      seed_e,
+      [=](int64_t occ, int32_t(&row)[1], float(&w)[1]) {
+        if (occ < batch) {
+          row[0] = ~(int32_t)occ;
+          w[0] = 1.f;
+        } else if (occ < 2 * batch) {
+          row[0] = users[occ - batch];
+          w[0] = -coef_pos[occ - batch];
+        } else {
+          row[0] = ~(int32_t)(occ - batch);  // g[B + j], j = occ - 2B
+          w[0] = 1.f;
+        }
+      },
+      [=](int32_t r) { return r >= 0 ? out + (int64_t)r * D : g + (int64_t)(~r) * D; });
 }
 
 // batch, m >= 1 with B M and 2B + M below 2^31; *n = 2B + M
@@ -511,9 +437,10 @@ static int launch_ssh_forward(const float *out, const float *emb, int64_t n_user
   hipLaunchKernelGGL((ssh_scores_kernel<D>), sg, dim3(256), 0, st, out, n_users, batch, m, users,
                      shared, temp, coef);
   MIREC_LAUNCH_CHECK();
-  hipLaunchKernelGGL((ssh_rows_kernel<D>), dim3((unsigned)((batch + m + kShWaves - 1) / kShWaves)),
-                     dim3(256), 0, st, out, emb, n_users, batch, m, users, pos, shared, mask, temp,
-                     grad_scale, coef, coef_pos, terms, reg, reg_shared, keys, vals);
+  const dim3 rg((unsigned)((batch + m + kSeedWaves - 1) / kSeedWaves));
+  hipLaunchKernelGGL((ssh_rows_kernel<D>), rg, dim3(256), 0, st, out, emb, n_users, batch, m,
+                     users, pos, shared, mask, temp, grad_scale, coef, coef_pos, terms, reg,
+                     reg_shared, keys, vals);
   MIREC_LAUNCH_CHECK();
   constexpr int TC = D < 64 ? D : 64;
   constexpr int TR = 2 * (256 / (TC / 4));
@@ -521,22 +448,6 @@ static int launch_ssh_forward(const float *out, const float *emb, int64_t n_user
   hipLaunchKernelGGL((ssh_g_kernel<D>), dim3((unsigned)(nb_user + nb_shared), D / TC), dim3(256),
                      0, st, out, n_users, batch, m, users, pos, shared, coef, coef_pos, nb_user,
                      g);
-  MIREC_LAUNCH_CHECK();
-  return MIREC_OK;
-}
-
-template <int D>
-static int launch_ssh_seed_accum(const float *out, const float *emb, int64_t batch, int64_t m,
-                                 const int32_t *users, const float *coef_pos, const float *g,
-                                 const int32_t *ks, const int32_t *vs, float decay,
-                                 float grad_scale, float layer_div, float *seed_p, float *seed_e,
-                                 hipStream_t st) {
-  constexpr int G = 64 / (D / 4);
-  const int64_t per_block = (int64_t)kShWaves * G;
-  const int64_t n = 2 * batch + m;
-  hipLaunchKernelGGL((ssh_seed_accum_kernel<D>), dim3((unsigned)((n + per_block - 1) / per_block)),
-                     dim3(256), 0, st, out, emb, batch, m, users, coef_pos, g, ks, vs, decay,
-                     grad_scale, layer_div, seed_p, seed_e);
   MIREC_LAUNCH_CHECK();
   return MIREC_OK;
 }
@@ -602,10 +513,7 @@ extern "C" int mirec_ssm_shared_seed_workspace(int64_t batch, int64_t m, int64_t
   int64_t n = 0;
   MIREC_CHECK_ARG(bytes != nullptr && n_nodes > 0 && ssh_shape(batch, m, &n));
   size_t tb = 0;
-  int rc = ssh_sort_bytes(n, n_nodes, &tb);
-  if (rc != MIREC_OK) return rc;
-  *bytes = ssh_align(tb) + ssh_align((size_t)n * sizeof(int32_t));
-  return MIREC_OK;
+  return seed_ws_layout(n, n_nodes, &tb, bytes);
 }
 
 extern "C" int mirec_ssm_shared_seed(const float *out, const float *emb, int64_t n_nodes,
@@ -623,29 +531,16 @@ extern "C" int mirec_ssm_shared_seed(const float *out, const float *emb, int64_t
   MIREC_CHECK_ARG(ssh_shape(batch, m, &n));
   MIREC_CHECK_ARG(n_layers >= 0 && n_users > 0 && n_nodes > n_users && n_nodes < INT32_MAX);
   if (!dim_supported(dim)) return MIREC_ERR_ARG;
-  size_t tb = 0;
-  int rc = ssh_sort_bytes(n, n_nodes, &tb);
-  if (rc != MIREC_OK) return rc;
-  const size_t need = ssh_align(tb) + ssh_align((size_t)n * sizeof(int32_t));
-  if (workspace_bytes < need) return MIREC_ERR_WORKSPACE;
-  char *ws = static_cast<char *>(workspace);
-  int32_t *vals_sorted = reinterpret_cast<int32_t *>(ws + ssh_align(tb));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (n <= kSmallSortMax) {
-    MIREC_HIP(small_sort_pairs(ws, tb, keys, keys_sorted, vals, vals_sorted, n, st));
-  } else {
-    size_t tb2 = tb;
-    MIREC_HIP(hipcub::DeviceRadixSort::SortPairs(ws, tb2, keys, keys_sorted, vals, vals_sorted,
-                                                 (int)n, 0, ssh_end_bit(n_nodes), st));
-  }
-  hipLaunchKernelGGL(ssh_heads_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                     keys_sorted, n, slot);
-  MIREC_LAUNCH_CHECK();
+  int32_t *vals_sorted = nullptr;
+  int rc = seed_sort_heads(keys, vals, n, n_nodes, workspace, workspace_bytes, keys_sorted,
+                           &vals_sorted, slot, st);
+  if (rc != MIREC_OK) return rc;
   const float layer_div = (float)(n_layers + 1);
   switch (dim) {
 #define C(DD) \
   case DD:    \
-    return launch_ssh_seed_accum<DD>(out, emb, batch, m, users, coef_pos, g, keys_sorted, vals_sorted, decay, grad_scale, layer_div, seed_p, seed_e, st);
+    return launch_seed_accum<DD>(ssh_seed_accum_kernel<DD>, n, st, out, emb, batch, m, users, coef_pos, g, keys_sorted, vals_sorted, decay, grad_scale, layer_div, seed_p, seed_e);
     C(4) C(8) C(16) C(32) C(64) C(128) C(256)
 #undef C
   }

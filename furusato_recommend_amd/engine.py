@@ -483,25 +483,23 @@ class PropagationEngine:
         self._acc_full = None
 
     # ------------------------------------------------------------ internals
-    def _ensure_ws(self, batch: int):
+    def _grow_ws(self, query, what: str, *shape):
+        """The sort workspace holds at least query(*shape, n_nodes, &bytes) bytes."""
         nb = ctypes.c_size_t(0)
-        check(lib.mirec_bpr_seed_workspace(batch, self.g.n_nodes, ctypes.byref(nb)),
-              "bpr_seed_workspace")
+        check(query(*shape, self.g.n_nodes, ctypes.byref(nb)), what)
         if nb.value > self._ws_bytes:
             self._ws = torch.empty(nb.value, dtype=torch.uint8, device=self.g.device)
             self._ws_bytes = nb.value
+
+    def _ensure_ws(self, batch: int):
+        self._grow_ws(lib.mirec_bpr_seed_workspace, "bpr_seed_workspace", batch)
 
     def _ensure_ssm(self, batch: int, n_neg: int):
         if self.g_u is None:
             f32 = dict(dtype=torch.float32, device=self.g.device)
             self.coef_pos = torch.empty(self.max_batch, **f32)
             self.g_u = torch.empty(self.max_batch, self.dim, **f32)
-        nb = ctypes.c_size_t(0)
-        check(lib.mirec_ssm_seed_workspace(batch, n_neg, self.g.n_nodes, ctypes.byref(nb)),
-              "ssm_seed_workspace")
-        if nb.value > self._ws_bytes:
-            self._ws = torch.empty(nb.value, dtype=torch.uint8, device=self.g.device)
-            self._ws_bytes = nb.value
+        self._grow_ws(lib.mirec_ssm_seed_workspace, "ssm_seed_workspace", batch, n_neg)
 
     def _ensure_ssm_shared(self, batch: int, m: int):
         if self._shared is None:
@@ -511,12 +509,7 @@ class PropagationEngine:
                                 g=torch.empty(B + M, self.dim, **f32),
                                 reg=torch.empty(M, **f32),
                                 mask=torch.empty(B * M, dtype=torch.uint8, device=dev))
-        nb = ctypes.c_size_t(0)
-        check(lib.mirec_ssm_shared_seed_workspace(batch, m, self.g.n_nodes, ctypes.byref(nb)),
-              "ssm_shared_seed_workspace")
-        if nb.value > self._ws_bytes:
-            self._ws = torch.empty(nb.value, dtype=torch.uint8, device=self.g.device)
-            self._ws_bytes = nb.value
+        self._grow_ws(lib.mirec_ssm_shared_seed_workspace, "ssm_shared_seed_workspace", batch, m)
         return self._shared
 
     def _prop(self, *, in_mode, x_in=None, seed_in=None, seed=None, addend=None, seed2=None,
@@ -1063,6 +1056,11 @@ class PropagationEngine:
         return self.loss
 
     # -------------------------------------------------------- sampled softmax
+    @staticmethod
+    def _check_temp(name: str, temp):
+        if not (float(temp) > 0.0 and math.isfinite(float(temp))):
+            raise ValueError(f"{name}: temp must be positive and finite, got {temp!r}")
+
     def _ssm_shape(self, users, neg):
         """(B, K) of an SSM batch: int32 ``neg`` of shape [B, K], K <= n_neg."""
         B = int(users.shape[0])
@@ -1094,8 +1092,7 @@ class PropagationEngine:
         ``temp``: loss = mean_t (logsumexp(s+_t, s_t,.) - s+_t) + decay *
         sum_t reg_t / B (K = 1, temp = 1 is bpr())."""
         B, K = self._ssm_shape(users, neg)
-        if not (float(temp) > 0.0 and math.isfinite(float(temp))):
-            raise ValueError(f"ssm: temp must be positive and finite, got {temp!r}")
+        self._check_temp("ssm", temp)
         if not self._masks_ready:
             self.frontier_ssm(users, pos, neg)  # the seed set S for the backward
         self._ensure_ssm(B, K)
@@ -1160,8 +1157,7 @@ class PropagationEngine:
         out of that pair's softmax; the shared rows' norms enter the reg term
         once per slot."""
         B, M = self._ssm_shared_shape(users, shared)
-        if not (float(temp) > 0.0 and math.isfinite(float(temp))):
-            raise ValueError(f"ssm_shared: temp must be positive and finite, got {temp!r}")
+        self._check_temp("ssm_shared", temp)
         if not self._masks_ready:
             self.frontier_ssm_shared(users, pos, shared)  # the seed set S for the backward
         b = self._ensure_ssm_shared(B, M)
@@ -1218,12 +1214,7 @@ class PropagationEngine:
                             torch.empty(n, D, dtype=torch.float32, device=dev),
                             torch.empty(n, dtype=torch.int32, device=dev))
         mp, me, mk = self._merged
-        nb = ctypes.c_size_t(0)
-        check(lib.mirec_seed_merge_workspace(n, self.g.n_nodes, ctypes.byref(nb)),
-              "seed_merge_workspace")
-        if nb.value > self._ws_bytes:
-            self._ws = torch.empty(nb.value, dtype=torch.uint8, device=self.g.device)
-            self._ws_bytes = nb.value
+        self._grow_ws(lib.mirec_seed_merge_workspace, "seed_merge_workspace", n)
         check(lib.mirec_seed_merge(keys.data_ptr(), rows_p.data_ptr(), rows_e.data_ptr(), n,
                                    self.dim, self.g.n_nodes, self.slot.data_ptr(), mp.data_ptr(),
                                    me.data_ptr(), mk.data_ptr(), self._ws.data_ptr(),
@@ -1316,6 +1307,23 @@ class PropagationEngine:
         self.compute_frontier(users, pos, neg)
         return self.forward(emb, pruned=self.prune)
 
+    def _step(self, emb: torch.Tensor, adam: AdamState, dropout, frontier, loss, batch, *args):
+        """One training step: ``frontier(*batch)``, the (pruned) forward,
+        ``loss(out, emb, *batch, *args)``, backward with fused Adam; under
+        ``dropout`` = (keep_prob, seed) on that edge-dropped graph, which is
+        cleared again whether or not the step completes."""
+        if dropout is not None:
+            self.set_dropout(*dropout)
+        try:
+            frontier(*batch)
+            out = self.forward(emb, pruned=self.prune)
+            res = loss(out, emb, *batch, *args)
+            self.backward(emb, adam=adam)
+        finally:
+            if dropout is not None:
+                self.set_dropout(None)
+        return res
+
     def train_step(self, emb: torch.Tensor, adam: AdamState, users, pos, neg, decay: float,
                    loss_accum: torch.Tensor | None = None, dropout=None) -> torch.Tensor:
         """stageOne: forward, BPR, backward, fused Adam.  Returns loss (device).
@@ -1326,19 +1334,8 @@ class PropagationEngine:
         a new seed per step (dropout_seed).  Frontier pruning stays on: the
         structural frontier S ∪ N(S) contains the dropped graph's, so the
         rows and neighbours it skips are exact zeros under any mask too."""
-        if dropout is None:
-            out = self.forward_for_batch(emb, users, pos, neg)
-            loss = self.bpr(out, emb, users, pos, neg, decay, loss_accum)
-            self.backward(emb, adam=adam)
-            return loss
-        self.set_dropout(*dropout)
-        try:
-            out = self.forward_for_batch(emb, users, pos, neg)
-            loss = self.bpr(out, emb, users, pos, neg, decay, loss_accum)
-            self.backward(emb, adam=adam)
-        finally:
-            self.set_dropout(None)
-        return loss
+        return self._step(emb, adam, dropout, self.compute_frontier, self.bpr,
+                          (users, pos, neg), decay, loss_accum)
 
     def train_step_ssm(self, emb: torch.Tensor, adam: AdamState, users, pos, neg, decay: float,
                        temp: float, loss_accum: torch.Tensor | None = None,
@@ -1346,17 +1343,8 @@ class PropagationEngine:
         """train_step with the sampled-softmax loss: frontier of the batch's
         (2 + K) B nodes, (pruned) forward, ssm(), backward, fused Adam; no
         host synchronisation.  ``neg`` is [B, K]; ``dropout`` as train_step's."""
-        if dropout is not None:
-            self.set_dropout(*dropout)
-        try:
-            self.frontier_ssm(users, pos, neg)
-            out = self.forward(emb, pruned=self.prune)
-            loss = self.ssm(out, emb, users, pos, neg, decay, temp, loss_accum)
-            self.backward(emb, adam=adam)
-        finally:
-            if dropout is not None:
-                self.set_dropout(None)
-        return loss
+        return self._step(emb, adam, dropout, self.frontier_ssm, self.ssm,
+                          (users, pos, neg), decay, temp, loss_accum)
 
     def train_step_ssm_shared(self, emb: torch.Tensor, adam: AdamState, users, pos, shared,
                               decay: float, temp: float,
@@ -1365,17 +1353,8 @@ class PropagationEngine:
         """train_step_ssm with one shared negative set ``shared`` [M] for the
         whole batch: frontier of its 2B + M nodes, (pruned) forward,
         ssm_shared(), backward, fused Adam; no host synchronisation."""
-        if dropout is not None:
-            self.set_dropout(*dropout)
-        try:
-            self.frontier_ssm_shared(users, pos, shared)
-            out = self.forward(emb, pruned=self.prune)
-            loss = self.ssm_shared(out, emb, users, pos, shared, decay, temp, loss_accum)
-            self.backward(emb, adam=adam)
-        finally:
-            if dropout is not None:
-                self.set_dropout(None)
-        return loss
+        return self._step(emb, adam, dropout, self.frontier_ssm_shared, self.ssm_shared,
+                          (users, pos, shared), decay, temp, loss_accum)
 
 
 def sample_shared(m_items: int, n_sets: int, m: int, seed: int, offset: int, out):

@@ -6,8 +6,10 @@ check that a refactor of a kernel's source leaves the machine code alone.
 For every kernel symbol of either library it compares the instruction text
 (addresses and encodings stripped; a branch keeps its pc-relative operand and
 its <kernel+offset> target, and a pc-relative literal that reaches read-only
-data is replaced by the address it forms, so a kernel that grew does not mark
-the ones after it) and the scalar fields of the kernel's entry in the code object's metadata
+data is replaced by the address it forms, or by the name of the out-of-line
+device function it reaches, and the s_nop padding behind a kernel is dropped,
+so a kernel that grew or a function that left does not mark the others) and
+the scalar fields of the kernel's entry in the code object's metadata
 note (VGPR/SGPR/AGPR counts, LDS, scratch, kernarg size, spills...).  Prints
 the kernels added, removed and changed; exits 1 if there are any.  Runs on
 the CPU with the ROCm llvm tools (the unbundling is isa_scan's)."""
@@ -33,6 +35,13 @@ def kernels(so: str) -> dict:
                 cur[m.group(1)] = m.group(2)
                 if m.group(1) == "name":
                     meta[m.group(2)] = cur
+        # a literal that reaches a function of the code object (a call of a
+        # device function kept out of line) is named after it: the function
+        # moves when the code object's other contents change size
+        syms = subprocess.run([f"{isa_scan.LLVM}/llvm-readelf", "-sW", co],
+                              capture_output=True, text=True, check=True).stdout
+        funcs = {int(m.group(1), 16): m.group(2) for m in
+                 re.finditer(r"^\s*\d+:\s+([0-9a-f]+)\s+\d+\s+FUNC\s.*\s(\S+)$", syms, re.M)}
         for fn, lines in isa_scan.disassembly(co).items():
             text, pc = [], None
             for line in lines:
@@ -45,9 +54,12 @@ def kernels(so: str) -> dict:
                 # the literal moves with the kernel, the address it forms does not
                 lit = re.match(r"(s_add_u32 .+, )(0x[0-9a-f]+)$", insn) if pc else None
                 if lit:
-                    insn = f"{lit.group(1)}<{(pc + int(lit.group(2), 16)) & 0xffffffff:#x}>"
+                    to = (pc + int(lit.group(2), 16)) & 0xffffffff
+                    insn = f"{lit.group(1)}<{funcs.get(to, hex(to))}>"
                 pc = int(addr.group(1), 16) + 4 if insn.startswith("s_getpc_b64") and addr else None
                 text.append(insn + (" " + target.group(0) if target else ""))
+            while text and text[-1] in ("s_nop 0", "..."):  # the padding up to the next function
+                text.pop()
             out[fn] = (text, meta.get(fn, {}))
     return out
 
